@@ -7,7 +7,10 @@ reference's t = 1 schedule fires them) over one batch of synthetic reads.
 The timed region is ONE CLEAN BUILD: `--steps` batches into an empty filter, so
 `build_time_s` is the BASELINE "CQF build time" for steps x 832 M k-mers (20 steps =
 16.6 G k-mers = the README's C. elegans data set, BASELINE.json configs[1]); warm-up
-steps run on a scratch filter of the same geometry. The build's command line follows the
+steps run on a scratch filter of the same geometry. A build is at most BUILD_STEPS batches:
+more steps time further clean builds of the same batches, each into a fresh filter (the clock
+stops while one filter is replaced by the next), so memory and the work of a step stay those of
+one C. elegans-sized build whatever `--steps` is. The build's command line follows the
 README recipe (-N = the k-mers presented, -n = the genome's k-mers, -e = the generator's
 error rate, sizing as src/CQF-deNoise.cpp:96-161) and is checked against a model of the
 filter's occupancy before it runs (sh-assembly_amd/shk/plan.py, tests/test_plan.py).
@@ -16,7 +19,10 @@ N > 1 (driver launches via torch.distributed.run): the filter is sharded by quot
 range, every rank hashes its own batch, bins the key words by owner and exchanges them
 with one RCCL all-to-all before its local insert. Weak scaling: reads per rank fixed.
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0. A plain run sets up, warms up, times the steps and reports them (with the
+per-kernel HIP-event times of the timed region); `--full` adds what takes runs of its own: the serial second build
+the per-kernel costs come from, the secondary rates (Contiger, PCIe-inclusive) and the CPU baseline.
+`--dump-outputs DIR` writes what the timed build leaves its caller after the last step (see dump_outputs).
 """
 import argparse
 import ctypes as C
@@ -35,6 +41,7 @@ HBM_PEAK = 8.0e12                 # MI355X_MICROARCH.md: 8 TB/s spec
 NAME_W = 11                       # digits in the read name
 PART = 1 << 23                    # the reference's part size (CQF_mt.h:743)
 OVERHEAD = 65535                  # CQF_mt.h:742
+BUILD_STEPS = 20                  # batches of one clean build: the README's C. elegans data set (16.6 G k-mers)
 
 
 def sizing(K, n_true, N_total, alpha, fr=0.0):
@@ -211,6 +218,25 @@ def cpu_baseline(torch, text_cpu, offs, lens, k, qb, budget_s=12.0):
     return out
 
 
+def dump_outputs(d, ctx, last, sample_blocks=65536, seed=7):
+    """what the timed build hands its caller after the last step, as .npy files in `d`: that step's statistics
+    (shk_batch_stats), the filter's counters (shk_totals) and .cqf header, and the bytes of a fixed, seeded sample of
+    the table's blocks (the whole table is 0.75 GB at the default size). Values are exact in float64 / float32.
+    A sharded filter: rank 0's shard."""
+    import numpy as np
+    import shk
+    os.makedirs(d, exist_ok=True)
+    t = ctx.totals()
+    np.save(os.path.join(d, "step_stats.npy"),
+            np.array([last.get(k, float("nan")) for k, _ in shk.BatchStats._fields_], dtype=np.float64))
+    np.save(os.path.join(d, "totals.npy"), np.array([getattr(t, k) for k, _ in shk.Totals._fields_], dtype=np.float64))
+    np.save(os.path.join(d, "header.npy"), np.frombuffer(ctx.header(), dtype=np.uint8).astype(np.float32))
+    blocks = np.frombuffer(ctx.blocks(), dtype=np.uint8).reshape(t.nblocks, -1)
+    idx = np.sort(np.random.default_rng(seed).choice(t.nblocks, min(sample_blocks, t.nblocks), replace=False))
+    np.save(os.path.join(d, "table_block_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(d, "table_blocks.npy"), blocks[idx].astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -222,9 +248,12 @@ def main():
     ap.add_argument("--max-load", type=float, default=0.95, help="predicted peak load above which deNoise rounds are added to the formula's (shk/plan.py)")
     ap.add_argument("--threads", type=int, default=0, help="threads per workgroup (0 = library default)")
     ap.add_argument("--ablate", type=int, default=0, help="diagnostics: SHK_ABLATE bits applied to the timed steps only")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also the measurements beside the headline: serial second build (per-kernel costs), "
+                                                        "secondary rates, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the timed build computed by its last step as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--serial", action="store_true", help="one batch after the other on one stream (shk_count_chunks) instead of the overlapped front end")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary measurements (PCIe-inclusive rate, Contiger on the built filter)")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary measurements (PCIe-inclusive rate, Contiger on the built filter)")
     ap.add_argument("--trace", action="store_true", help="diagnostics: print the filter's counters after every step (adds a sync per step)")
     ap.add_argument("--force-dist", action="store_true", help="run the sharded/all-to-all code path even with one rank")
     ap.add_argument("--full-build", action="store_true", help="the whole C. elegans-sized build (README.md:90-91: 16.5 G k-mers = 20 steps, no warm-up)")
@@ -273,7 +302,8 @@ def main():
     # Weak scaling: with G GPUs the data set is G times larger (G x the genome, G x the reads per step) and
     # so is the filter: every GPU keeps a C. elegans-sized shard.
     G_total = args.genome * world
-    pl = plan.plan_build(K, G_total, L, ERR, R * kmers_per_read * world / len(offs), len(offs) * args.steps,
+    B = min(args.steps, BUILD_STEPS)     # batches per clean build; the generated batches are those of one build
+    pl = plan.plan_build(K, G_total, L, ERR, R * kmers_per_read * world / len(offs), len(offs) * B,
                          world=world, max_load=args.max_load)
     qb, nd, trigger = pl["qb"], pl["rounds"], pl["trigger"]
     if args.qb:
@@ -288,7 +318,7 @@ def main():
     genome = torch.randint(0, 4, (G_total,), device=device, dtype=torch.uint8,
                            generator=torch.Generator(device=device).manual_seed(2))
     texts = [gen_batch_torch(torch, genome, R, L, ERR, (s * world + rank) * R, 1000 + s * world + rank, device)
-             for s in range(args.steps)]
+             for s in range(B)]
     torch.cuda.synchronize()
     if args.host_text:
         texts = [t.cpu().pin_memory() for t in texts]
@@ -375,6 +405,7 @@ def main():
                         (s,) + tuple(1e3 * (tm[i + 1] - tm[i]) for i in range(4)) + (self.sstate.collectives,)), file=sys.stderr, flush=True)
                 if s + 1 == nsteps:
                     shkdist.check(ctx, self.sstate)
+            self.last = st
             self.counted += st["kmers"]
             self.removed += st["removed"]
             self.rounds += st["denoise_rounds"]
@@ -388,63 +419,78 @@ def main():
     if args.warmup:
         # untimed passes over the first batches into a scratch filter (same geometry, same schedule): loads the code
         # objects, sizes the lazily allocated buffers' pools, warms RCCL
-        w = Run()
-        w.ctx.profile(True)     # (the timed run records HIP events per kernel: let the runtime grow its event / signal pools here)
+        w = None
         for s in range(args.warmup):
-            w.step(s % args.steps, args.steps)
+            if s % B == 0:          # (a fresh scratch filter for every B warm-up steps, as for the timed builds)
+                if w:
+                    w.ctx.close()
+                w = Run()
+                w.ctx.profile(True)     # (the timed run records HIP events per kernel: let the runtime grow its event / signal pools here)
+            w.step(s % B, B)
         for ex in w.inflight.values():     # (the exchange a pipelined warm-up step started for a batch it never counted)
             ex.wait()
         torch.cuda.synchronize()
         w.ctx.close()
         del w
-    run = Run()
-    ctx = run.ctx
-    tot = ctx.totals()
     if args.ablate:
         os.environ["SHK_ABLATE"] = str(args.ablate)
-    ctx.profile(True)
-    ctx.profile_reset()
-    if dist:
-        dist.barrier()
-    torch.cuda.synchronize()
     if os.environ.get("SHK_DIST_STACKS"):      # diagnostics: where the threads are, every 100 ms of the timed region
         import faulthandler
         import threading
         print("threads:", [t.name for t in threading.enumerate()], file=sys.stderr, flush=True)
         faulthandler.dump_traceback_later(0.1, repeat=True, file=sys.stderr)
-    t0 = time.perf_counter()
-    for s in range(args.steps):
-        run.step(s, args.steps)
-    torch.cuda.synchronize()
+    # the timed steps: clean builds of at most B batches, each into a fresh filter; only the builds are timed
+    dt, prof, run = 0.0, {}, None
+    counted = removed_total = rounds_fired = 0
+    for first in range(0, args.steps, B):
+        n = min(B, args.steps - first)
+        if run:
+            run.ctx.close()
+        run = Run()
+        ctx = run.ctx
+        tot = ctx.totals()
+        ctx.profile(True)
+        ctx.profile_reset()
+        if dist:
+            dist.barrier()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for s in range(n):
+            run.step(s, n)
+        torch.cuda.synchronize()
+        if dist:
+            dist.barrier()
+        dt += time.perf_counter() - t0
+        for k, (launches, ms) in ctx.profile_get().items():
+            a = prof.get(k, (0, 0.0))
+            prof[k] = (a[0] + launches, a[1] + ms)
+        counted, removed_total, rounds_fired = counted + run.counted, removed_total + run.removed, rounds_fired + run.rounds
     if os.environ.get("SHK_DIST_STACKS"):
         faulthandler.cancel_dump_traceback_later()
-    if dist:
-        dist.barrier()
-    dt = time.perf_counter() - t0
     if sharded and rank == 0 and os.environ.get("SHK_DIST_TIMING"):
         print("small collectives: %d, %.1f ms in all (build %.1f ms); phases hash+route+exchange / wait / stage / count: %s ms" % (
             shkdist.COLLECTIVE_SECONDS[1], 1e3 * shkdist.COLLECTIVE_SECONDS[0], 1e3 * dt, ["%.0f" % (1e3 * x) for x in getattr(run, "phase_s", [])] + ["lib %.0f" % (1e3 * shkdist.HASH_EXCHANGE_SECONDS[0]), "exch %.0f" % (1e3 * shkdist.HASH_EXCHANGE_SECONDS[1])]),
               file=sys.stderr, flush=True)
-    prof = ctx.profile_get()
     end = ctx.totals()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ctx, run.last)
     if dist:
         tt = torch.tensor([dt], dtype=torch.float64, device=device)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
-    counted, removed_total, rounds_fired = run.counted, run.removed, run.rounds
 
     # In the overlapped build the front end of batch s+1 and the rebuild of batch s share the chip: a kernel's HIP-event
     # span then includes the time it waits for CUs the other stream holds (k_roll_scatter: 4.6 ms on its own, ~19 ms
     # next to the rebuild). What each kernel COSTS is therefore taken from a second, untimed build of the same batches,
     # one after the other on one stream (shk_count_chunks), with the same events.
     serial_prof, serial_dt = None, None
-    if rank == 0 and world == 1 and not sharded and not args.serial and not args.host_text and not args.ablate:
+    if args.full and rank == 0 and world == 1 and not sharded and not args.serial and not args.host_text and not args.ablate:
         r2 = Run()
         r2.ctx.profile(True)
         r2.ctx.profile_reset()
         torch.cuda.synchronize()
         ts = time.perf_counter()
-        for s in range(args.steps):
+        for s in range(B):
             r2.ctx.count_chunks(texts[s].data_ptr(), offs, lens, on_device=True, text_bytes=texts[s].numel())
         torch.cuda.synchronize()
         serial_dt = time.perf_counter() - ts
@@ -501,7 +547,7 @@ def main():
                                    "%d steps x %d reads/step/GPU, 8 MiB chunks; warm-up on a scratch filter"
                                    % (args.genome, pl["N"], pl["n"], pl["qb"], pl["qb"] + 8, pl["formula_rounds"], pl["formula_trigger"],
                                       nd, trigger, pl["predicted_peak_load"], args.max_load, args.steps, R),
-                       "kmers_per_step_per_gpu": R * kmers_per_read, "denoise_rounds_fired": rounds_fired,
+                       "kmers_per_step_per_gpu": R * kmers_per_read, "steps_per_build": B, "denoise_rounds_fired": rounds_fired,
                        "removed": removed_total, "parallelism": "quotient-range shards x%d" % world,
                        "final_nelts": (run.sstate.nelts if sharded else end.nelts), "final_ndistinct": (run.sstate.ndistinct if sharded else end.ndistinct),
                        "predicted_peak_load": pl["predicted_peak_load"]},
@@ -523,10 +569,10 @@ def main():
         }
         if serial_prof:
             out["serial_build"] = {"what": "the same batches through shk_count_chunks, one after the other on one stream (untimed second build)",
-                                   "ms_per_step": serial_dt / args.steps * 1e3,
+                                   "ms_per_step": serial_dt / B * 1e3,
                                    "kernel_ms": {k: round(v[1], 3) for k, v in serial_prof.items()},
                                    "kernel_launches": {k: int(v[0]) for k, v in serial_prof.items()}}
-        if not args.no_secondary and world == 1 and not args.host_text and not args.ablate:
+        if args.full and not args.no_secondary and world == 1 and not args.host_text and not args.ablate:
             # outside the timed region: what the headline value leaves out
             sec = {}
             try:
@@ -538,7 +584,7 @@ def main():
             except shk.ShkError as e:
                 sec["host_text"] = {"error": str(e)}
             out["secondary"] = sec
-        if not args.no_cpu_baseline and world == 1:   # reported on rank 0 at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:   # reported on rank 0 at N = 1 only
             text_cpu = texts[0].cpu().numpy().tobytes()
             out["cpu_baseline"] = cpu_baseline(torch, text_cpu, offs, lens, K, qb)
         os.write(json_fd, (json.dumps(out) + "\n").encode())

@@ -1044,13 +1044,13 @@ def test_config5_error_profile_sizing_and_qb33_filter(tmp_path):
 # ---------------------------------------------------------------- the driver's bench contract
 @pytest.mark.gpu
 def test_bench_prints_one_json_line_with_the_contract_fields():
-    """`python bench.py --gpus 1 --steps K --warmup W` as the driver runs it (shorter): stdout is exactly one JSON line with
-    the metric fields, the path-level `roofline` and the `cpu_baseline` of the compiled reference"""
+    """`python bench.py --gpus 1 --steps K --warmup W --full` as the driver runs it (shorter): stdout is exactly one JSON line
+    with the metric fields, the path-level `roofline` and the `cpu_baseline` of the compiled reference"""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--full"],
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -1067,6 +1067,43 @@ def test_bench_prints_one_json_line_with_the_contract_fields():
     assert cb["kind"] == "reference" and cb["unit"] == "k-mers/s" and cb["cores"] >= 1 and cb["value"] > 1e6 and cb["sample"]
     # every k-mer of the build was counted: steps x reads x (L - k + 1), minus the reads' N restarts
     assert d["build_kmers"] > 0.99 * 3 * 8_000_000 * 104
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_what_the_timed_build_computed(tmp_path):
+    """a plain `bench.py --gpus 1 --steps K --warmup W` times exactly K steps and leaves out what --full adds. K above
+    one build's 20 batches times further clean builds of the same batches (memory stays that of one build: 100 steps of
+    distinct batches would need 254 GB of FASTQ text). --dump-outputs writes the last step's statistics, the filter's
+    counters and header and a seeded sample of its blocks as float .npy files (64 MB at most), consistent with the JSON line"""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    import shk
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "100", "--warmup", "1",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert (d["steps"], d["warmup"], d["config"]["steps_per_build"]) == (100, 1, 20) and d["unit"] == "k-mers/s" and d["value"] > 1e9
+    assert abs(d["ms_per_step"] * 100 / 1e3 - d["build_time_s"]) < 1e-6
+    assert d["build_kmers"] > 0.99 * 100 * 8_000_000 * 104
+    assert not {"cpu_baseline", "secondary", "serial_build"} & set(d)
+    files = {f.name: np.load(f) for f in out.iterdir()}
+    assert set(files) == {"step_stats.npy", "totals.npy", "header.npy", "table_block_index.npy", "table_blocks.npy"}
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    assert sum(f.stat().st_size for f in out.iterdir()) <= 64 << 20
+    names = [k for k, _ in shk.Totals._fields_]
+    t = dict(zip(names, files["totals.npy"]))
+    assert (t["nelts"], t["ndistinct"]) == (d["config"]["final_nelts"], d["config"]["final_ndistinct"])
+    st = dict(zip([k for k, _ in shk.BatchStats._fields_], files["step_stats.npy"]))
+    assert 0.99 * 8_000_000 * 104 < st["kmers"] <= 8_000_000 * 104
+    idx, blk = files["table_block_index.npy"], files["table_blocks.npy"]
+    assert np.all(np.diff(idx) > 0) and 0 <= idx[0] and idx[-1] < t["nblocks"]
+    assert blk.shape == (len(idx), t["table_bytes"] // t["nblocks"]) and blk.max() <= 255 and blk.any()
 
 
 def test_overlapped_front_end_matches_oracle():

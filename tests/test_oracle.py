@@ -270,12 +270,11 @@ def test_reference_slot_access_overruns_its_allocation_without_the_guard():
     may fill the tail without corrupting the checker's heap."""
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    if not os.path.exists("/root/reference/cqf/gqf.c"):
-        pytest.skip("needs the reference sources to build the ASan probe")
-    subprocess.check_call(["make", "-s", "-C", os.path.join(root, "oracle"), "asan"])
-    probe = os.path.join(root, "oracle", "_ref", "asan_probe")
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0")       # qf_destroy leaks the lock array (gqf.c:2306-2317)
-    env.pop("LD_PRELOAD", None)
+    probe = os.path.join(root, "oracle", "_ref", "asan_probe")     # built beside libshk_ref.so (oracle/Makefile `all`)
+    if not os.path.exists(probe):
+        pytest.skip("oracle/_ref/asan_probe not built (no reference sources at build time)")
+    # qf_destroy leaks the lock array (gqf.c:2306-2317); a library preloaded ahead of the ASan runtime is tolerated
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:verify_asan_link_order=0")
     ok = subprocess.run([probe], env=env, capture_output=True, text=True)
     assert ok.returncode == 0 and "probe ok" in ok.stdout, ok.stderr[-2000:]
     bad = subprocess.run([probe], env=dict(env, REF_NO_GUARD="1"), capture_output=True, text=True)

@@ -1,5 +1,6 @@
 import sys, os
-sys.path.insert(0,'/root/repo/sh-assembly_amd'); sys.path.insert(0,'/root/repo/tests'); sys.path.insert(0,'/root/repo')
+ROOT=os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0,os.path.join(ROOT,'sh-assembly_amd')); sys.path.insert(0,os.path.join(ROOT,'tests')); sys.path.insert(0,ROOT)
 import torch, shk, bench
 import torch.distributed as dist
 os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT="29533", RANK="0", WORLD_SIZE="1")
