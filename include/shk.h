@@ -164,8 +164,7 @@ int shk_count_words(shk_ctx *ctx, const uint64_t *d_words, uint64_t nwords, uint
  *                      shk_stage_point_* / shk_stage_round_try below, which continue the walk from shard to shard
  *                      over the single table's layout */
 typedef struct shk_summary {
-  uint64_t new_distinct, added, removed, before;
-  uint64_t hist[32];
+  uint64_t new_distinct, added, removed;
   uint32_t err_bits;       /* raw kernel flags; SHK_SOFT_BITS are meaningless for a speculative range */
   uint32_t reserved;
 } shk_summary;
@@ -192,27 +191,26 @@ int shk_stage_words(shk_ctx *ctx, const uint64_t *d_words, uint64_t nwords);
  * and the records of a deNoise point (for callers that keep set-up and steady state apart). Idempotent. */
 int shk_route_reserve(shk_ctx *ctx);
 int shk_stage_words_pair(shk_ctx *ctx, const uint64_t *d_words_a, uint64_t nwords_a, const uint64_t *d_words_b, uint64_t nwords_b);
-int shk_stage_summary(shk_ctx *ctx, uint32_t chunk_lo, uint32_t chunk_hi, uint32_t hist_base, uint32_t hist_shift,
-                      int want_hist, shk_summary *out);
+int shk_stage_summary(shk_ctx *ctx, uint32_t chunk_lo, uint32_t chunk_hi, int want_chunks, shk_summary *out);
 int shk_stage_commit(shk_ctx *ctx, uint32_t chunk_lo, uint32_t chunk_hi, const shk_summary *s);
 /* try/accept form (what sh-assembly_amd/shk/dist.py uses): shk_stage_try computes everything about
  * inserting [lo, hi] that does not depend on the other ranks' decision -- statistics, run lengths and
  * encodings (kept on the device), free pointers, error flags -- and writes nothing to the live table;
  * shk_stage_accept then places the runs into the spare table and makes it the live one (only after a
  * clean try over the same range); a try that is not accepted is simply superseded by the next call */
-int shk_stage_try(shk_ctx *ctx, uint32_t chunk_lo, uint32_t chunk_hi, uint32_t hist_base, uint32_t hist_shift,
-                  int want_hist, shk_summary *out);
+int shk_stage_try(shk_ctx *ctx, uint32_t chunk_lo, uint32_t chunk_hi, int want_chunks, shk_summary *out);
 int shk_stage_accept(shk_ctx *ctx, const shk_summary *s);
 /* One deNoise round on this shard fused with the insertion of the staged chunks [lo, hi] that lie behind the deNoise
  * point (one pass over the table instead of two): statistics only; shk_stage_accept writes. out->removed = singletons
  * dropped; a dropped key that reappears in [lo, hi] counts in out->new_distinct. If any rank reports err_bits, or the
  * trigger would be reached again inside [lo, hi], do not accept: run shk_denoise and go on as usual. */
 int shk_stage_try_denoise(shk_ctx *ctx, uint32_t chunk_lo, uint32_t chunk_hi, shk_summary *out);
-/* want_hist = 2 in shk_stage_summary / shk_stage_try additionally records the first chunk of every
+/* want_chunks != 0 in shk_stage_summary / shk_stage_try additionally records the first chunk of every
  * new key; this call returns the exact histogram of that last pass: out[i] = new keys first seen in
  * chunk i, for i < n (n <= chunk_hi + 1 of the pass). With it the ranks find the chunk of a deNoise
- * point in one pass instead of refining the 32-bin histogram. SHK_ERR_ARG when the last pass has none.
- * (The first want_hist = 2 pass allocates nregions KiB of device memory for the first-chunk records.) */
+ * point in one pass. SHK_ERR_ARG when the last pass has none.
+ * (The first such pass allocates nregions KiB of device memory for the first-chunk records, unless
+ * the context was created for deNoise rounds or shards, which allocates them up front.) */
 int shk_stage_chunk_hist(shk_ctx *ctx, uint64_t *out, uint32_t n);
 
 /* ---- a deNoise point inside the staged batch in ONE rebuild per shard (the sharded form of what shk_count_chunks does

@@ -19,6 +19,9 @@
 
 #define SHK_EMPTY 0xFFFFFFFFu
 #define SHK_SUM_STRIDE 8
+#define SHK_CNT_NOVER 4                                              // counters[]: 0-3 the statistics of a pass (ShkMergeArgs), then
+#define SHK_CNT_ISLOTS 5                                             // regions on the over list, slots of the intermediate table
+#define SHK_NCOUNTERS 6
 #define SHK_SPILL_LENS SHK_REGION                                   // one length byte per quotient
 #define SHK_SPILL_STRIDE 768                                         // + the lanes' staged run bytes, packed: a filled region needs
                                                                      // about 250 of the 512; one that needs more than the record holds is rebuilt from the list
@@ -31,7 +34,7 @@ struct ShkMergeArgs {
   const uint8_t *tabA;
   uint8_t *tabB;
   const uint64_t *finA;         // [nregions+1] free pointer at each region start of A
-  uint64_t *finB;               // same for B (write pass input; written by the single-launch rebuild)
+  uint64_t *finB;               // same for B (write pass input)
   const uint32_t *words;        // 32-bit records sorted by region (written by the last partition level); null when there are none
   const uint64_t *region_base;  // [nregions+1] offsets into words; with region_cap: [nregions] END offsets, region r starts at r * region_cap
   uint32_t region_cap;          // 0, or the fixed capacity of a region's slot in `words` (ShkRpLevel::slot_cap)
@@ -39,16 +42,13 @@ struct ShkMergeArgs {
   uint64_t q_lo;
   uint32_t hb;
   uint32_t chunk_lo, chunk_hi;    // only words whose chunk index lies in [lo, hi] take part
-  uint32_t hist_base, hist_shift; // coarse histogram of the first chunk of every NEW key
-  int want_hist;                  // 0: totals only (the common case: no deNoise point inside the batch)
+  int want_hist;                  // 1: record the first chunk of every NEW key in `newchunks` (0: totals only, the common
+                                  // case: no deNoise point inside the batch)
   int denoise;                    // 1: drop entries whose count is exactly 1 (no new keys)
   uint32_t *summary;              // [SHK_SUM_STRIDE*nregions]: T, c (relative to the region start; 0 = empty),
-                                  // new distinct, occurrences added, removed, new before hist_base
-  unsigned long long *counters;   // 0 new distinct, 1 occurrences added, 2 removed, 3 new before hist_base
-  unsigned long long *hist;       // [SHK_HIST_BINS]
+                                  // new distinct, occurrences added, removed, FUSED: occurrences added up to the split
+  unsigned long long *counters;   // 0 new distinct, 1 occurrences added, 2 removed, 3 FUSED: occurrences added up to the split
   uint32_t *err;
-  unsigned long long *lb_agg;     // [nregions] look-back records of the single-launch rebuild (zeroed per launch)
-  unsigned long long *lb_incl;    // [nregions]
   unsigned long long *dbg;        // diagnostics only: per-phase cycle sums of sampled regions (null = off)
   uint32_t ablate;                // diagnostics only (SHK_ABLATE): skip phases to time them; results invalid
   // spill scheme (MODE 3 -> k_region_scan_* -> k_region_place): the summary launch keeps every region's
@@ -204,21 +204,18 @@ __device__ __forceinline__ void shk_store_image(const ShkMergeArgs &A, uint32_t 
   }
 }
 
-// MODE 0: summary (lengths + statistics). MODE 1: write pass of the two-launch scheme
-// (free pointers come from k_region_scan_*). MODE 3: summary that also spills the run lengths
-// and encodings for k_region_place. MODE 2: single launch -- the wave obtains its
-// free pointer by looking back at the regions before it (see k_region_merge docs below).
+// MODE 0: summary (lengths + statistics). MODE 3: summary that also spills the run lengths and
+// encodings for k_region_place. MODE 1: write pass (free pointers come from k_region_scan_*) for
+// the regions whose runs did not fit the spill record.
 #define SHK_STAGE_PER_LANE 32   // bytes of encoded run kept per lane between the length pass and placement
 #define SHK_STAGE_STRIDE 36     // lanes 9 dwords apart: byte i of every lane's area falls into a different LDS bank
-#define SHK_LB_VALID 0x80000000u
-#define SHK_LB_INCL (1ULL << 63)
 
 #define SHK_STAMP(i) do { if (A.dbg && (blockIdx.x & 63) == 0 && threadIdx.x == 0) { unsigned long long t_ = __builtin_amdgcn_s_memtime(); atomicAdd(&A.dbg[i], t_ - t_prev); t_prev = t_; } } while (0)
 
 template <int MODE, int IMGB, bool FUSED = false>
 __global__ void __launch_bounds__(SHK_MERGE_GROUP) k_region_merge(ShkMergeArgs A) {
   static_assert(!FUSED || MODE == 3, "the one-pass deNoise point is a spill-mode pass");
-  constexpr bool WRITE = MODE == 1 || MODE == 2;   // builds the image and stores table B
+  constexpr bool WRITE = MODE == 1;                // builds the image and stores table B
   constexpr bool STAGE = WRITE || MODE == 3;       // keeps the runs' encodings per lane
   // LDS image of IMGB blocks: the region's own blocks + the blocks its runs may spill into.
   // IMGB = IMG_BLOCKS normally; the host retries a pass with IMG_BLOCKS_BIG when a cluster is longer.
@@ -252,9 +249,6 @@ __global__ void __launch_bounds__(SHK_MERGE_GROUP) k_region_merge(ShkMergeArgs A
   // cycles). The words live in `orend`, which is idle until the fold is over -- 512 bytes more would push the plain
   // kernel's LDS over an allocation step and cost it a workgroup per CU (measured: 12.6 -> 13.7 ms).
   uint32_t *hidle = reinterpret_cast<uint32_t *>(orend);
-  // the coarse histogram of the merge pass lives in `orunw`, which only the rank/select step in front of the join uses
-  static_assert(sizeof(uint64_t) * IMG_BLOCKS >= sizeof(uint32_t) * SHK_HIST_BINS, "lhist fits orunw");
-  uint32_t *lhist = reinterpret_cast<uint32_t *>(orunw);
 
   unsigned long long t_prev = A.dbg ? __builtin_amdgcn_s_memtime() : 0;
   const unsigned tid = threadIdx.x;
@@ -487,13 +481,11 @@ __global__ void __launch_bounds__(SHK_MERGE_GROUP) k_region_merge(ShkMergeArgs A
   // (each lane sorted only its own quotients' segments)
   __syncthreads();                       // join: the old structure is in place (the helper wave leaves here)
   if (s_fail & SHK_E_CORRUPT) fatal = true;
-  if (tid < SHK_HIST_BINS) lhist[tid] = 0;   // (orunw is free from here on)
-  shk_wave_sync();
 
   SHK_STAMP(3);   // counting sort + per-quotient sort
   // ---- one pass over the quotients: merge old run and new keys -> run length, statistics,
   // and (write modes) the run's encoding staged per lane
-  uint32_t my_new = 0, my_removed = 0, my_before = 0;
+  uint32_t my_new = 0, my_removed = 0;
   // (region-relative free-pointer functions: 32-bit arithmetic inside the kernel)
   ShkMPw mine; mine.a = 0; mine.b = SHK_NEG_INF_W;
   ShkMPw mine_i; mine_i.a = 0; mine_i.b = SHK_NEG_INF_W;   // FUSED: the same for the intermediate table
@@ -547,7 +539,7 @@ __global__ void __launch_bounds__(SHK_MERGE_GROUP) k_region_merge(ShkMergeArgs A
       }
       uint64_t total = 0;
       bool is_new = false;
-      uint32_t mc = 0, nhx = 0;
+      uint32_t nhx = 0;
       if (FUSED) {
         // one-pass deNoise point: cb = the key's count when the round runs (old + chunks <= split), ca = what arrives behind it
         uint64_t cb = take_old ? ocnt : 0, ca = 0;
@@ -608,7 +600,7 @@ __global__ void __launch_bounds__(SHK_MERGE_GROUP) k_region_merge(ShkMergeArgs A
       } else is_new = true;
       if (take_new) {
         total += hcnt[nh];
-        mc = nkey & (SHK_MAX_CHUNKS - 1); nhx = nh;
+        nhx = nh;
         ni++;
         ncomp = NONE;
         if (ni < ne) { nh = nidx[ni]; nkey = hkey[nh]; ncomp = nkey >> SHK_CHUNK_BITS; }
@@ -617,16 +609,8 @@ __global__ void __launch_bounds__(SHK_MERGE_GROUP) k_region_merge(ShkMergeArgs A
       }
       if (!FUSED && is_new) {
         my_new++;
-        if (MODE != 1 && A.want_hist) {
-          // exact mode: the key is only flagged here and its first chunk collected below (the count
-          // was consumed above); the coarse histogram would cost one global atomic per bin and region
-          if (A.newchunks) hcnt[nhx] |= 0x80000000u;
-          else if (mc < A.hist_base) my_before++;
-          else {
-            uint32_t bin = (mc - A.hist_base) >> A.hist_shift;
-            atomicAdd(&lhist[bin < SHK_HIST_BINS ? bin : SHK_HIST_BINS - 1], 1u);
-          }
-        }
+        // the key is only flagged here and its first chunk collected below (the count was consumed above)
+        if (MODE != 1 && A.want_hist && A.newchunks) hcnt[nhx] |= 0x80000000u;
       }
       const unsigned el = shk_enc_len_fast(rem, total);
       if (STAGE) {
@@ -678,16 +662,16 @@ __global__ void __launch_bounds__(SHK_MERGE_GROUP) k_region_merge(ShkMergeArgs A
   tot.a = __builtin_amdgcn_readlane(incl.a, SHK_WAVE - 1);
   { const int tb = __builtin_amdgcn_readlane(incl.b, SHK_WAVE - 1); tot.b = tb > 0 ? tb : SHK_NEG_INF; }
   pre.a = 0; pre.b = SHK_NEG_INF;
-  if (MODE == 1 || MODE == 2) {   // (only the placement needs the function in front of every lane)
+  if (MODE == 1) {   // (only the placement needs the function in front of every lane)
     pre.a = __shfl_up(incl.a, 1);
     { const int pb = __shfl_up(incl.b, 1); pre.b = pb > 0 ? pb : SHK_NEG_INF; }
     if (tid == 0) { pre.a = 0; pre.b = SHK_NEG_INF; }
   }
 
-  // per-region statistics (summed later by k_region_scan_c / k_stats_reduce: no same-address atomics)
+  // per-region statistics (summed later by k_region_scan_c: no same-address atomics)
   if (MODE != 1) {
     const uint32_t t_added = shk_wave_incl_add(my_added), t_new = shk_wave_incl_add(my_new),
-                   t_removed = shk_wave_incl_add(my_removed), t_before = shk_wave_incl_add(FUSED ? my_added_b : my_before);
+                   t_removed = shk_wave_incl_add(my_removed), t_before = FUSED ? shk_wave_incl_add(my_added_b) : 0;
     if (tid == SHK_WAVE - 1) {
       uint32_t *sm = A.summary + (size_t)SHK_SUM_STRIDE * r;
       sm[0] = fatal ? 0 : (uint32_t)tot.a;
@@ -697,7 +681,6 @@ __global__ void __launch_bounds__(SHK_MERGE_GROUP) k_region_merge(ShkMergeArgs A
       if (tot.a > 0xFFFF) atomicOr(A.err, SHK_E_RUN_TOO_LONG);
       if (s_fail) atomicOr(A.err, s_fail);
     }
-    if (A.want_hist && !A.newchunks && tid < SHK_HIST_BINS && lhist[tid]) atomicAdd(&A.hist[tid], (unsigned long long)lhist[tid]);
   }
   SHK_STAMP(5);   // scan + statistics
   if (MODE != 1 && A.want_hist && A.newchunks && !fatal) {
@@ -748,83 +731,8 @@ __global__ void __launch_bounds__(SHK_MERGE_GROUP) k_region_merge(ShkMergeArgs A
   if (MODE == 0 || (A.ablate & 128)) return;
 
   // ================= placement =================
-  long long fin_rel, fout_rel;
-  if (MODE == 1) {
-    fin_rel = (long long)A.finB[r] - (long long)q0;
-    fout_rel = (long long)A.finB[r + 1] - (long long)q0;
-  } else {
-    // ---- single launch: look back over the regions before this one.
-    // Every region publishes (T, c) as soon as it knows them (lb_agg) and its outgoing free
-    // pointer once it knows its own incoming one (lb_incl). A window r'..r-1 composes to
-    // f -> max(f + a, b); since no region's runs may end more than IMG_SLOTS behind its
-    // start, f_in(r') <= start(r') + IMG_SLOTS - SHK_REGION, so the window already decides
-    // f_in(r) = b as soon as start(r') + IMG_SLOTS - SHK_REGION + a <= b.
-    if (tid == 0) {
-      const uint32_t c_rel = (!fatal && tot.b > 0) ? (uint32_t)tot.b : 0;
-      __hip_atomic_store(&A.lb_agg[r], (unsigned long long)(SHK_LB_VALID | ((uint32_t)tot.a << 12)) << 32 | c_rel,
-                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    long long f_in = 0;
-    bool done = (r == 0) || (A.ablate & 32);
-    ShkMP win; win.a = 0; win.b = SHK_NEG_INF;       // composition of the regions already walked (nearest first)
-    uint32_t back = 0;                                // regions walked so far
-    uint32_t spins = 0;
-    while (!done) {
-      const long long rr = (long long)r - 1 - back - tid;   // this lane's predecessor
-      unsigned long long incl_w = 0, agg_w = 0;
-      if (rr >= 0) {
-        incl_w = __hip_atomic_load(&A.lb_incl[rr], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (!(incl_w & SHK_LB_INCL)) agg_w = __hip_atomic_load(&A.lb_agg[rr], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      const bool has_incl = rr >= 0 && (incl_w & SHK_LB_INCL);
-      const bool has_agg = rr >= 0 && ((agg_w >> 32) & SHK_LB_VALID);
-      const bool ready = rr < 0 || has_incl || has_agg;
-      // lanes are ordered nearest-first; use the prefix of lanes that are ready
-      const unsigned long long ready_m = __ballot(ready);
-      const unsigned nready = ready_m == ~0ULL ? 64u : (unsigned)(__ffsll((long long)~ready_m) - 1);
-      const unsigned long long stop_m = __ballot(rr < 0 || has_incl);   // lanes that end the walk
-      // compose lane by lane (wave-uniform loop over the ready prefix)
-      unsigned used = 0;
-      for (; used < nready; used++) {
-        const long long rr_u = (long long)r - 1 - back - used;
-        if ((stop_m >> used) & 1) {
-          const unsigned long long iw = __shfl(incl_w, used);
-          const long long fo = rr_u < 0 ? 0 : (long long)(iw & ~SHK_LB_INCL);
-          f_in = shk_mp_apply(win, fo);
-          done = true;
-          break;
-        }
-        const unsigned long long aw = __shfl(agg_w, used);
-        ShkMP m;
-        m.a = (long long)(((aw >> 32) & 0x7FFFFFFFu) >> 12);
-        const uint32_t c_rel = (uint32_t)aw;
-        m.b = c_rel ? rr_u * SHK_REGION + c_rel : SHK_NEG_INF;
-        win = shk_mp_compose(m, win);      // farther region first, then what we had
-        const long long bound = rr_u * SHK_REGION + (IMG_SLOTS - SHK_REGION);
-        if (bound + win.a <= win.b) { f_in = win.b; done = true; break; }
-      }
-      if (!done) {
-        back += used;
-        if (used == 0) {
-          if (++spins > (1u << 18)) { if (tid == 0) atomicOr(A.err, SHK_E_LOOKBACK); fatal = true; break; }
-          __builtin_amdgcn_s_sleep(8);
-        }
-      }
-    }
-    // tot is in region-relative slots; f_in is absolute
-    const long long f_out = fatal ? 0 : shk_mp_apply(tot, f_in - (long long)q0) + (long long)q0;
-    if (tid == 0 && !(fatal && spins > (1u << 18)))
-      __hip_atomic_store(&A.lb_incl[r], SHK_LB_INCL | (unsigned long long)f_out, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (tid == 0) {
-      A.finB[r + 1] = (uint64_t)f_out;
-      if (r == 0) A.finB[0] = 0;
-      if (tot.a > 0 && f_out - (long long)q0 > IMG_SLOTS) atomicOr(A.err, SHK_E_NEW_EXTENT);
-      if ((uint64_t)f_out > A.xnslots) atomicOr(A.err, SHK_E_TABLE_FULL);
-    }
-    fin_rel = f_in - (long long)q0;
-    fout_rel = f_out - (long long)q0;
-  }
-  SHK_STAMP(6);   // look-back
+  const long long fin_rel = (long long)A.finB[r] - (long long)q0;
+  const long long fout_rel = (long long)A.finB[r + 1] - (long long)q0;
   if (fatal) return;
   const uint32_t out_lo = fin_rel > 0 ? (uint32_t)fin_rel : 0;
   const bool new_any = tot.a > 0;
@@ -1039,20 +947,6 @@ __global__ void k_chunk_hist(const uint16_t *newchunks, const uint32_t *summary,
     if (lh[i]) atomicAdd(&chist[i], (unsigned long long)lh[i]);
 }
 
-// statistics of a single-launch rebuild (MODE 2): sum the per-region records
-__global__ void k_stats_reduce(const uint32_t *summary, uint32_t nregions, unsigned long long *counters) {
-  __shared__ uint64_t scratch64[SHK_MAX_WAVES + 1];
-  const uint32_t per = SHK_RSCAN_TILE / blockDim.x;
-  const uint32_t r0 = blockIdx.x * SHK_RSCAN_TILE + threadIdx.x * per;
-  for (int z = 0; z < 4; z++) {
-    uint64_t v = 0;
-    for (uint32_t j = 0; j < per; j++)
-      if (r0 + j < nregions) v += summary[(size_t)SHK_SUM_STRIDE * (r0 + j) + 2 + z];
-    const uint64_t t = shk_block_sum64(v, scratch64);
-    if (threadIdx.x == 0 && t) atomicAdd(&counters[z], (unsigned long long)t);
-  }
-}
-
 // ---------------------------------------------------------------- free pointers
 // fin[r+1] = max(fin[r] + T_r, region start + c_r), as a 3-launch scan over tiles of regions.
 __device__ __forceinline__ ShkMP shk_region_mp(const uint32_t *summary, uint32_t r, uint32_t nregions, uint32_t stride = SHK_SUM_STRIDE) {
@@ -1162,7 +1056,7 @@ __global__ void k_region_scan_c(const uint32_t *summary, uint32_t nregions, cons
   }
   if (stride == 2) {        // intermediate table of a one-pass deNoise point: slots in use (its shard's share of the free-pointer function)
     const uint64_t t = shk_block_sum64(slots, scratch64);
-    if (threadIdx.x == 0 && t) atomicAdd(&counters[4 + SHK_HIST_BINS + 1], (unsigned long long)t);
+    if (threadIdx.x == 0 && t) atomicAdd(&counters[SHK_CNT_ISLOTS], (unsigned long long)t);
   }
   // statistics of this tile's regions
   if (stride >= 6)

@@ -28,11 +28,11 @@
 
 enum {
   KP_COUNT_LINES, KP_SCAN_CHUNKS, KP_EMIT_READS, KP_COUNT_KEYS, KP_HASH, KP_SCAN, KP_RP_PREP, KP_RP_HIST,
-  KP_RP_SCATTER, KP_MERGE_SUM, KP_REGION_SCAN, KP_MERGE_WRITE, KP_MERGE_SINGLE, KP_MERGE_SPILL, KP_PLACE, KP_MARKS, KP_LOOKUP, KP_WALK, KP_UG_WALK, KP_UG_FINISH, KP_MERGE_FUSED, KP_MERGE_SAMPLE, KP_MISC, KP_ROLL_HIST, KP_ROLL_SCATTER, KP_PACK, KP_RP_SLOTS, KP_N
+  KP_RP_SCATTER, KP_MERGE_SUM, KP_REGION_SCAN, KP_MERGE_WRITE, KP_MERGE_SPILL, KP_PLACE, KP_MARKS, KP_LOOKUP, KP_WALK, KP_UG_WALK, KP_UG_FINISH, KP_MERGE_FUSED, KP_MERGE_SAMPLE, KP_MISC, KP_ROLL_HIST, KP_ROLL_SCATTER, KP_PACK, KP_RP_SLOTS, KP_N
 };
 static const char *kp_names[KP_N] = {
   "k_count_lines", "k_scan_chunks", "k_emit_reads", "k_count_keys", "k_hash_reads", "k_scan_*", "k_rp_prep",
-  "k_rp_hist", "k_rp_scatter", "k_region_merge<summary>", "k_region_scan", "k_region_merge<write>", "k_region_merge<single>",
+  "k_rp_hist", "k_rp_scatter", "k_region_merge<summary>", "k_region_scan", "k_region_merge<write>",
   "k_region_merge<spill>", "k_region_place", "k_denoise_marks", "k_lookup", "k_extend_forward+k_select_seeds", "k_ug_walk", "k_ug_check/emit/median/links", "k_region_merge<fused>", "k_region_merge<sample>", "misc", "k_roll_hist", "k_roll_scatter", "k_pack_reads", "k_rp_slot_cursors"};
 
 struct PendingEvent { int id; hipEvent_t a, b; };
@@ -75,11 +75,10 @@ struct shk_ctx {
   uint32_t *d_tfb;
   uint32_t *d_summary;
   long long *d_tile_a, *d_tile_b, *d_tile_f;
-  unsigned long long *d_lb_agg, *d_lb_incl;
+  uint64_t *d_dump_offs;        // [nregions + 2] shk_dump: where every region's entries start in the output
   int big_image;                // 1: rebuild kernels run with the SHK_IMG_BLOCKS_BIG image (set after a cluster outgrew the small one)
-  int single_ok;                // 1: single-launch rebuild with look-back (SHK_SINGLE=1); 0 after it had to give up once
   uint32_t merge_group;         // threads per region workgroup (one wave rebuilds; the others help staging and folding)
-  int use_spill;                // 1 (default): summary launch spills lengths + encodings, k_region_place writes table B
+  // the summary launch spills lengths + encodings per region, k_region_place writes table B from them
   uint8_t *d_spill;
   uint32_t *d_over_list;
   // what the spill records currently describe (a write pass may use them only for the same request)
@@ -98,9 +97,9 @@ struct shk_ctx {
   int slots_off;
   uint32_t pt_lo, pt_split, pt_hi; int pt_valid; uint64_t pt_nprot;   // one-pass deNoise point in progress (shk_stage_point_*)
   const uint64_t *pt_words;     // its words (null: a round on its own, shk_stage_round_try)
-  unsigned long long *d_counters;  // 4 counters + 32 hist bins
+  unsigned long long *d_counters;  // [SHK_NCOUNTERS]
   uint32_t *d_err;
-  uint64_t *h_pinned;           // pinned mirror: counters(4) hist(32) err(1) scalars(4)
+  uint64_t *h_pinned;           // pinned mirror: counters [0, SHK_NCOUNTERS), err [40], scalars [41, 64)
   uint64_t max_reads;
   // profiling
   int prof_on;
@@ -150,7 +149,7 @@ static void prof_collect(shk_ctx *c) {
 static int map_err_bits(uint32_t bits) {
   if (!bits) return SHK_OK;
   if (bits & SHK_E_TABLE_FULL) return SHK_ERR_TABLE_FULL;
-  if (bits & (SHK_E_OLD_EXTENT | SHK_E_NEW_EXTENT | SHK_E_HASH_FULL | SHK_E_RUN_TOO_LONG | SHK_E_LOOKBACK)) return SHK_ERR_REGION;
+  if (bits & (SHK_E_OLD_EXTENT | SHK_E_NEW_EXTENT | SHK_E_HASH_FULL | SHK_E_RUN_TOO_LONG)) return SHK_ERR_REGION;
   if (bits & SHK_E_CORRUPT) return SHK_ERR_CORRUPT;
   if (bits & SHK_E_BAD_FASTQ) return SHK_ERR_FASTQ;
   if (bits & SHK_E_KEYS_FULL) return SHK_ERR_BATCH;
@@ -263,11 +262,9 @@ extern "C" int shk_create(const shk_config *cfg, shk_ctx **out) {
   }
   if (dmalloc(&c->d_tfb, capk / SHK_RP_TILE + 2)) return SHK_ERR_HIP;
   if (dmalloc(&c->d_summary, SHK_SUM_STRIDE * (uint64_t)c->nregions + 8)) return SHK_ERR_HIP;
-  if (dmalloc(&c->d_lb_agg, (uint64_t)c->nregions + 2) || dmalloc(&c->d_lb_incl, (uint64_t)c->nregions + 2)) return SHK_ERR_HIP;
-  c->single_ok = getenv("SHK_SINGLE") ? 1 : 0;
+  if (dmalloc(&c->d_dump_offs, (uint64_t)c->nregions + 2)) return SHK_ERR_HIP;
   c->merge_group = SHK_MERGE_GROUP;
   if (const char *mg = getenv("SHK_MERGE_GROUP")) { int v = atoi(mg); if (v == 64 || v == 128) c->merge_group = (uint32_t)v; }
-  c->use_spill = (getenv("SHK_TWO_LAUNCH") || c->single_ok) ? 0 : 1;
   // the sampled location of a deNoise point needs enough regions for the sample to mean something
   c->region_cap = 0; c->slot_overflows = 0; c->slots_off = getenv("SHK_NO_SLOTS") ? 1 : 0;
   c->stage2_b = nullptr; c->stage2_na = c->stage2_nb = 0;
@@ -280,7 +277,7 @@ extern "C" int shk_create(const shk_config *cfg, shk_ctx **out) {
   if (dmalloc(&c->d_spill, (uint64_t)c->nregions * SHK_SPILL_STRIDE) || dmalloc(&c->d_over_list, (uint64_t)c->nregions + 1)) return SHK_ERR_HIP;
   { uint64_t nt = c->nregions / SHK_RSCAN_TILE + 2;
     if (dmalloc(&c->d_tile_a, nt) || dmalloc(&c->d_tile_b, nt) || dmalloc(&c->d_tile_f, nt)) return SHK_ERR_HIP; }
-  if (dmalloc(&c->d_counters, 4 + SHK_HIST_BINS + 4)) return SHK_ERR_HIP;
+  if (dmalloc(&c->d_counters, SHK_NCOUNTERS)) return SHK_ERR_HIP;
   if (dmalloc(&c->d_err, 4)) return SHK_ERR_HIP;
   HIPCHK(hipHostMalloc((void **)&c->h_pinned, 64 * sizeof(uint64_t), hipHostMallocDefault));
   HIPCHK(hipMemsetAsync(c->tab[0], 0, c->table_bytes + SHK_SLACK, c->stream));
@@ -292,7 +289,7 @@ extern "C" int shk_create(const shk_config *cfg, shk_ctx **out) {
   // A context that is going to take deNoise rounds (its own, or as a shard of a filter that does) gets the buffers of the
   // first-chunk records and of the one-pass point now: allocating gigabytes inside a counting call is a synchronous trip
   // into the driver in the middle of the build (contexts without rounds never pay for them)
-  if ((cfg->num_denoise > 0 || cfg->num_shards > 1) && c->use_spill && !getenv("SHK_COARSE_HIST")) {
+  if (cfg->num_denoise > 0 || cfg->num_shards > 1) {
     if (ensure_chist(c) || point_alloc(c)) { shk_destroy(c); return SHK_ERR_HIP; }
   }
   if (cfg->num_shards > 1 && !getenv("SHK_ROUTE_SINGLE_BUFFER")) {     // the two send buffers of shk_route_words, for the same reason
@@ -317,7 +314,7 @@ extern "C" void shk_destroy(shk_ctx *c) {
   if (getenv("SHK_STAMPS")) {
     unsigned long long st[16];
     hipMemcpy(st, c->d_scalars + 16, sizeof(st), hipMemcpyDeviceToHost);
-    static const char *nm[9] = {"stage+init", "fold keys", "old rank/select", "count sort", "merge pass", "scan+stats", "look-back", "placement", "stores"};
+    static const char *nm[9] = {"stage+init", "fold keys", "old rank/select", "count sort", "merge pass", "scan+stats", "(unused)", "placement", "stores"};
     unsigned long long tot = 0; for (int i = 0; i < 9; i++) tot += st[i];
     for (int i = 0; i < 9; i++) fprintf(stderr, "SHK_STAMPS %-16s %6.2f %%\n", nm[i], tot ? 100.0 * st[i] / tot : 0.0);
   }
@@ -330,7 +327,7 @@ extern "C" void shk_destroy(shk_ctx *c) {
   hipFree(c->d_base[0]); hipFree(c->d_base_sub);
   for (uint32_t l = 0; l < c->nlevels; l++) { hipFree(c->d_hist[l]); hipFree(c->d_base[l + 1]); }
   if (c->d_isum) { hipFree(c->d_isum); hipFree(c->d_ilens); hipFree(c->d_fin_i); hipFree(c->d_prot); }
-  hipFree(c->d_spill); hipFree(c->d_over_list); if (c->d_newchunks) { hipFree(c->d_newchunks); hipFree(c->d_chist); hipHostFree(c->h_chist); } hipFree(c->d_cursor); hipFree(c->d_tfb); hipFree(c->d_summary); hipFree(c->d_lb_agg); hipFree(c->d_lb_incl); hipFree(c->d_tile_a); hipFree(c->d_tile_b); hipFree(c->d_tile_f); hipFree(c->d_counters); hipFree(c->d_err);
+  hipFree(c->d_spill); hipFree(c->d_over_list); if (c->d_newchunks) { hipFree(c->d_newchunks); hipFree(c->d_chist); hipHostFree(c->h_chist); } hipFree(c->d_cursor); hipFree(c->d_tfb); hipFree(c->d_summary); hipFree(c->d_dump_offs); hipFree(c->d_tile_a); hipFree(c->d_tile_b); hipFree(c->d_tile_f); hipFree(c->d_counters); hipFree(c->d_err);
   hipHostFree(c->h_pinned);
   hipStreamDestroy(c->stream);
   delete c;
@@ -649,33 +646,29 @@ static void launch_merge(shk_ctx *c, const ShkMergeArgs &A0) {
 }
 
 struct MergeOut {
-  uint64_t newd, added, removed, before;
-  uint64_t hist[SHK_HIST_BINS];
+  uint64_t newd, added, removed;
   uint32_t err;
-  int have_chist;               // c->h_chist[chunk] = new keys first seen in that chunk (exact)
 };
 
-static void fill_args(shk_ctx *c, ShkMergeArgs *A, const uint64_t *words, uint32_t lo, uint32_t hi, uint32_t hbase,
-                      uint32_t hshift, int denoise, int want_hist = 0) {
-  A->want_hist = want_hist;
+static void fill_args(shk_ctx *c, ShkMergeArgs *A, const uint64_t *words, uint32_t lo, uint32_t hi, int denoise) {
+  A->want_hist = 0;
   A->tabA = c->tab[c->cur]; A->tabB = c->tab[c->cur ^ 1];
   A->finA = c->fin[c->cur]; A->finB = c->fin[c->cur ^ 1];
   A->words = reinterpret_cast<const uint32_t *>(words); A->region_base = c->d_base[c->nlevels]; A->region_cap = c->region_cap;
   A->nslots = c->nslots; A->xnslots = c->xnslots; A->nblocks = c->nblocks; A->q_lo = c->q_lo; A->hb = c->cfg.hb;
-  A->chunk_lo = lo; A->chunk_hi = hi; A->hist_base = hbase; A->hist_shift = hshift; A->denoise = denoise;
+  A->chunk_lo = lo; A->chunk_hi = hi; A->denoise = denoise;
   A->ablate = 0;
 #ifdef SHK_DIAGNOSTICS   // timing ablations give INVALID results: compiled into diagnostic builds only (make DIAG=1)
   { const char *ab = getenv("SHK_ABLATE"); A->ablate = ab ? (uint32_t)atoi(ab) : 0; }
 #endif
-  A->lb_agg = c->d_lb_agg; A->lb_incl = c->d_lb_incl;
   { const char *sp = getenv("SHK_STAMPS");    // diagnostics: "fused" = only the one-pass deNoise launches, "plain" = all the others, else all
     A->dbg = (sp && strcmp(sp, "fused") != 0) ? (unsigned long long *)(c->d_scalars + 16) : nullptr; }
-  A->spill = c->d_spill; A->over_list = c->d_over_list; A->n_over = c->d_counters + 4 + SHK_HIST_BINS; A->list = nullptr;
+  A->spill = c->d_spill; A->over_list = c->d_over_list; A->n_over = c->d_counters + SHK_CNT_NOVER; A->list = nullptr;
   A->newchunks = nullptr; A->chist = nullptr;
   A->counted = c->counted;
   A->r0 = 0; A->rstride = 1;
   A->split = ~0u; A->isum = nullptr; A->ilens = nullptr; A->prot_list = nullptr; A->nprot = 0;
-  A->summary = c->d_summary; A->counters = c->d_counters; A->hist = c->d_counters + 4; A->err = c->d_err;
+  A->summary = c->d_summary; A->counters = c->d_counters; A->err = c->d_err;
 }
 
 // first request for the exact first-chunk histogram (contexts that never reach a deNoise point never pay for it)
@@ -686,21 +679,21 @@ static int ensure_chist(shk_ctx *c) {
   return SHK_OK;
 }
 
-// summary launch + free-pointer scan, then read the statistics back (one synchronisation)
-static int merge_summary(shk_ctx *c, const uint64_t *words, uint32_t lo, uint32_t hi, uint32_t hbase, uint32_t hshift,
-                         int denoise, MergeOut *o, int want_hist = 0, int spill = 0) {
+// summary launch + free-pointer scan, then read the statistics back (one synchronisation).
+// with_chist: the pass also records the first chunk of every new key; c->h_chist[lo..hi] afterwards.
+// spill: the summary keeps the runs for k_region_place (a write pass for the same request only places them)
+static int merge_summary(shk_ctx *c, const uint64_t *words, uint32_t lo, uint32_t hi, int denoise, MergeOut *o,
+                         bool with_chist, bool spill) {
   ShkMergeArgs A;
-  fill_args(c, &A, words, lo, hi, hbase, hshift, denoise, want_hist);
-  HIPCHK(hipMemsetAsync(c->d_counters, 0, (4 + SHK_HIST_BINS + 1) * 8, c->stream));
-  spill = spill && c->use_spill;
+  fill_args(c, &A, words, lo, hi, denoise);
+  HIPCHK(hipMemsetAsync(c->d_counters, 0, (SHK_CNT_NOVER + 1) * 8, c->stream));
   c->spill_valid = 0;
-  if (want_hist == 2 && !getenv("SHK_COARSE_HIST")) { int rc = ensure_chist(c); if (rc) return rc; }
-  const bool exact = want_hist == 2 && c->d_newchunks;
-  if (exact) {   // (zeroed in front of the pass: regions whose record overflows add to the histogram themselves)
-    A.newchunks = c->d_newchunks; A.chist = c->d_chist;
+  if (with_chist) {   // (zeroed in front of the pass: regions whose record overflows add to the histogram themselves)
+    int rc = ensure_chist(c);
+    if (rc) return rc;
+    A.want_hist = 1; A.newchunks = c->d_newchunks; A.chist = c->d_chist;
     HIPCHK(hipMemsetAsync(c->d_chist, 0, SHK_MAX_CHUNKS * 8, c->stream));
   }
-  o->have_chist = 0;
   if (spill) { ProfScope ps(c, KP_MERGE_SPILL);
     launch_merge<3>(c, A); }
   else { ProfScope ps(c, KP_MERGE_SUM);
@@ -711,26 +704,24 @@ static int merge_summary(shk_ctx *c, const uint64_t *words, uint32_t lo, uint32_
     hipLaunchKernelGGL(k_region_scan_b, dim3(1), dim3(c->threads), 0, c->stream, c->d_tile_a, c->d_tile_b, ntiles, c->d_tile_f);
     hipLaunchKernelGGL(k_region_scan_c, dim3(ntiles), dim3(c->threads), 0, c->stream, c->d_summary, c->nregions, c->d_tile_f,
                        c->xnslots, (uint32_t)(c->big_image ? SHK_IMG_BLOCKS_BIG * 64 : SHK_IMG_SLOTS), c->fin[c->cur ^ 1], c->d_counters, c->d_err); }
-  if (exact) {
+  if (with_chist) {
     ProfScope ps(c, KP_MISC);
     hipLaunchKernelGGL(k_chunk_hist, dim3((c->nregions + SHK_CHIST_REGIONS - 1) / SHK_CHIST_REGIONS), dim3(256), 0, c->stream,
                        c->d_newchunks, c->d_summary, c->nregions, c->d_chist);
     HIPCHK(hipMemcpyAsync(c->h_chist, c->d_chist, ((uint64_t)hi + 1) * 8, hipMemcpyDeviceToHost, c->stream));
   }
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(c->h_pinned, c->d_counters, (4 + SHK_HIST_BINS + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(c->h_pinned, c->d_counters, (SHK_CNT_NOVER + 1) * 8, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipMemcpyAsync(c->h_pinned + 40, c->d_err, 4, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
-  o->newd = c->h_pinned[0]; o->added = c->h_pinned[1]; o->removed = c->h_pinned[2]; o->before = c->h_pinned[3];
-  for (int i = 0; i < SHK_HIST_BINS; i++) o->hist[i] = c->h_pinned[4 + i];
+  o->newd = c->h_pinned[0]; o->added = c->h_pinned[1]; o->removed = c->h_pinned[2];
   o->err = *(uint32_t *)(c->h_pinned + 40);
   if (o->err) c->last_err_bits = o->err;
   if (o->err) HIPCHK(hipMemsetAsync(c->d_err, 0, 16, c->stream));
-  o->have_chist = exact ? 1 : 0;
-  c->chist_n = exact ? hi + 1 : 0;
+  c->chist_n = with_chist ? hi + 1 : 0;
   if (spill && !o->err) {
     c->spill_valid = 1; c->spill_words = words; c->spill_lo = lo; c->spill_hi = hi; c->spill_denoise = denoise;
-    c->spill_big = c->big_image; c->spill_nover = c->h_pinned[4 + SHK_HIST_BINS];
+    c->spill_big = c->big_image; c->spill_nover = c->h_pinned[SHK_CNT_NOVER];
   }
   return SHK_OK;
 }
@@ -738,7 +729,7 @@ static int merge_summary(shk_ctx *c, const uint64_t *words, uint32_t lo, uint32_
 // write launch for the summary that was just computed; then flip the live table
 static int merge_write(shk_ctx *c, const uint64_t *words, uint32_t lo, uint32_t hi, int denoise) {
   ShkMergeArgs A;
-  fill_args(c, &A, words, lo, hi, 0, 0, denoise);
+  fill_args(c, &A, words, lo, hi, denoise);
   HIPCHK(hipMemsetAsync(c->tab[c->cur ^ 1], 0, c->table_bytes, c->stream));
   if (c->spill_valid && c->spill_words == words && c->spill_lo == lo && c->spill_hi == hi && c->spill_denoise == denoise &&
       c->spill_big == c->big_image) {
@@ -767,60 +758,17 @@ static int merge_write(shk_ctx *c, const uint64_t *words, uint32_t lo, uint32_t 
   return SHK_OK;
 }
 
-// Single-launch rebuild: statistics and table B in one pass (free pointers by look-back).
-// The live table is NOT flipped here; the caller commits with commit_single() once it has
-// looked at the statistics (a deNoise point inside the range means the pass is discarded).
-static int merge_single(shk_ctx *c, const uint64_t *words, uint32_t lo, uint32_t hi, int denoise, MergeOut *o,
-                        int want_hist = 0, uint32_t hbase = 0, uint32_t hshift = 0) {
-  ShkMergeArgs A;
-  fill_args(c, &A, words, lo, hi, hbase, hshift, denoise, want_hist);
-  HIPCHK(hipMemsetAsync(c->d_counters, 0, (4 + SHK_HIST_BINS) * 8, c->stream));
-  HIPCHK(hipMemsetAsync(c->d_lb_agg, 0, ((uint64_t)c->nregions + 2) * 8, c->stream));
-  HIPCHK(hipMemsetAsync(c->d_lb_incl, 0, ((uint64_t)c->nregions + 2) * 8, c->stream));
-  HIPCHK(hipMemsetAsync(c->tab[c->cur ^ 1], 0, c->table_bytes, c->stream));
-  c->spill_valid = 0;
-  o->have_chist = 0;
-  c->chist_n = 0;
-  { ProfScope ps(c, KP_MERGE_SINGLE);
-    launch_merge<2>(c, A); }
-  { ProfScope ps(c, KP_REGION_SCAN);
-    const uint32_t ntiles = (c->nregions + SHK_RSCAN_TILE - 1) / SHK_RSCAN_TILE;
-    hipLaunchKernelGGL(k_stats_reduce, dim3(ntiles), dim3(c->threads), 0, c->stream, c->d_summary, c->nregions, c->d_counters); }
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(c->h_pinned, c->d_counters, (4 + SHK_HIST_BINS) * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipMemcpyAsync(c->h_pinned + 40, c->d_err, 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  o->newd = c->h_pinned[0]; o->added = c->h_pinned[1]; o->removed = c->h_pinned[2]; o->before = c->h_pinned[3];
-  for (int i = 0; i < SHK_HIST_BINS; i++) o->hist[i] = c->h_pinned[4 + i];
-  o->err = *(uint32_t *)(c->h_pinned + 40);
-  if (o->err) c->last_err_bits = o->err;
-  if (o->err) HIPCHK(hipMemsetAsync(c->d_err, 0, 16, c->stream));
-  if (o->err & SHK_E_LOOKBACK) c->single_ok = 0;
-  return SHK_OK;
-}
-static void commit_single(shk_ctx *c) { c->cur ^= 1; }
-
 static int denoise_round_once(shk_ctx *c, uint64_t *removed) {
   uint64_t ml = c->cfg.min_denoise_len ? c->cfg.min_denoise_len : (1ULL << 20);
   { ProfScope ps(c, KP_MARKS);
     hipLaunchKernelGGL(k_denoise_marks, dim3(1), dim3(64), 0, c->stream, c->tab[c->cur], c->nslots, c->xnslots, c->nblocks,
                        ml, (unsigned long long *)(c->d_scalars + 3)); }
   MergeOut o;
-  int rc;
-  bool done = false;
-  if (c->single_ok) {
-    rc = merge_single(c, nullptr, 0, 0, 1, &o);
-    if (rc) return rc;
-    if (!o.err) { commit_single(c); done = true; }
-    else if (!(o.err & SHK_E_LOOKBACK)) return map_err_bits(o.err);
-  }
-  if (!done) {
-    rc = merge_summary(c, nullptr, 0, 0, 0, 0, 1, &o, 0, 1);
-    if (rc) return rc;
-    if (o.err) return map_err_bits(o.err);
-    rc = merge_write(c, nullptr, 0, 0, 1);
-    if (rc) return rc;
-  }
+  int rc = merge_summary(c, nullptr, 0, 0, 1, &o, false, true);
+  if (rc) return rc;
+  if (o.err) return map_err_bits(o.err);
+  rc = merge_write(c, nullptr, 0, 0, 1);
+  if (rc) return rc;
   c->nelts -= o.removed;        // CQF_mt.h:1037-1038
   c->ndistinct -= o.removed;
   *removed = o.removed;
@@ -832,13 +780,12 @@ static int denoise_round_once(shk_ctx *c, uint64_t *removed) {
 // trigger would be reached again inside [lo, hi]: the caller then runs the plain round.
 static int denoise_with_rest(shk_ctx *c, const uint64_t *words, uint32_t lo, uint32_t hi, shk_batch_stats *st, bool *done) {
   *done = false;
-  if (!c->use_spill) return SHK_OK;
   uint64_t ml = c->cfg.min_denoise_len ? c->cfg.min_denoise_len : (1ULL << 20);
   { ProfScope ps(c, KP_MARKS);
     hipLaunchKernelGGL(k_denoise_marks, dim3(1), dim3(64), 0, c->stream, c->tab[c->cur], c->nslots, c->xnslots, c->nblocks,
                        ml, (unsigned long long *)(c->d_scalars + 3)); }
   MergeOut o;
-  int rc = merge_summary(c, words, lo, hi, lo, 0, 1, &o, 0, 1);
+  int rc = merge_summary(c, words, lo, hi, 1, &o, false, true);
   if (rc) return rc;
   if (o.err) return SHK_OK;
   if (c->rounds_left > 0 && c->ndistinct - o.removed + o.newd >= c->cfg.ndistinct_for_denoise) return SHK_OK;
@@ -901,7 +848,7 @@ static void point_scans(shk_ctx *c, bool final_table, bool inter_table, long lon
 
 static int point_read(shk_ctx *c, PointOut *po) {
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(c->h_pinned, c->d_counters, (4 + SHK_HIST_BINS + 2) * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(c->h_pinned, c->d_counters, SHK_NCOUNTERS * 8, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipMemcpyAsync(c->h_pinned + 40, c->d_err, 4, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   po->newd_after = c->h_pinned[0]; po->added_after = c->h_pinned[1]; po->removed = c->h_pinned[2]; po->added_before = c->h_pinned[3];
@@ -916,17 +863,17 @@ static int point_try(shk_ctx *c, const uint64_t *words, uint32_t lo, uint32_t sp
   if (rc) return rc;
   if (with_chist) { rc = ensure_chist(c); if (rc) return rc; }
   ShkMergeArgs A;
-  fill_args(c, &A, words, lo, hi, 0, 0, 1, 0);
+  fill_args(c, &A, words, lo, hi, 1);
   A.split = split; A.isum = c->d_isum; A.ilens = c->d_ilens;
   if (with_chist) {
-    A.want_hist = 2; A.newchunks = c->d_newchunks; A.chist = c->d_chist;
+    A.want_hist = 1; A.newchunks = c->d_newchunks; A.chist = c->d_chist;
     HIPCHK(hipMemsetAsync(c->d_chist, 0, SHK_MAX_CHUNKS * 8, c->stream));
   }
   { const char *sp = getenv("SHK_STAMPS");
     A.dbg = (sp && strcmp(sp, "plain") != 0) ? (unsigned long long *)(c->d_scalars + 16) : nullptr; }
   c->spill_valid = 0;
   c->chist_n = 0;
-  HIPCHK(hipMemsetAsync(c->d_counters, 0, (4 + SHK_HIST_BINS + 2) * 8, c->stream));
+  HIPCHK(hipMemsetAsync(c->d_counters, 0, SHK_NCOUNTERS * 8, c->stream));
   { ProfScope ps(c, KP_MERGE_FUSED);
     SHK_FOR_REGION_SLICES(c, A, nblk)
       hipLaunchKernelGGL((k_region_merge<3, SHK_IMG_BLOCKS, true>), dim3(nblk), dim3(c->merge_group), 0, c->stream, A); }
@@ -941,7 +888,7 @@ static int point_try(shk_ctx *c, const uint64_t *words, uint32_t lo, uint32_t sp
   HIPCHK(hipMemcpyAsync(c->h_pinned + 49, c->d_ilens, 1, hipMemcpyDeviceToHost, c->stream));
   rc = point_read(c, po);
   if (rc) return rc;
-  po->islots = c->h_pinned[4 + SHK_HIST_BINS + 1];
+  po->islots = c->h_pinned[SHK_CNT_ISLOTS];
   po->ifin = c->h_pinned[48];
   po->first_used = (c->h_pinned[49] & 0xff) != 0;
   if (with_chist && !po->err) c->chist_n = hi + 1;
@@ -982,9 +929,9 @@ static int point_finish(shk_ctx *c, const uint64_t *words, uint32_t lo, uint32_t
     std::vector<uint32_t> regs;
     for (uint64_t q : prot) { const uint32_t r = (uint32_t)(q >> SHK_REGION_LOG2); if (regs.empty() || regs.back() != r) regs.push_back(r); }
     ShkMergeArgs A;
-    fill_args(c, &A, words, lo, hi, 0, 0, 1, 0);
+    fill_args(c, &A, words, lo, hi, 1);
     A.split = split; A.isum = c->d_isum; A.ilens = c->d_ilens;
-    HIPCHK(hipMemsetAsync(c->d_counters, 0, (4 + SHK_HIST_BINS + 2) * 8, c->stream));
+    HIPCHK(hipMemsetAsync(c->d_counters, 0, SHK_NCOUNTERS * 8, c->stream));
     HIPCHK(hipMemcpyAsync(c->d_over_list, regs.data(), regs.size() * 4, hipMemcpyHostToDevice, c->stream));
     A.list = c->d_over_list; A.prot_list = c->d_prot; A.nprot = (uint32_t)nprot;
     { ProfScope ps(c, KP_MISC);
@@ -1008,7 +955,7 @@ static int denoise_fused(shk_ctx *c, const uint64_t *words, uint32_t lo, uint32_
                          shk_batch_stats *st, bool *done, bool verify = false, uint32_t *exact_ch = nullptr, int *crossing = nullptr) {
   *done = false;
   if (crossing) *crossing = -1;
-  if (!c->use_spill || c->big_image || c->single_ok || getenv("SHK_NO_FUSED_POINT")) return SHK_OK;
+  if (c->big_image || getenv("SHK_NO_FUSED_POINT")) return SHK_OK;
   PointOut po;
   int rc = point_try(c, words, lo, cstar, hi, verify, &po);
   if (rc) return rc;
@@ -1084,8 +1031,8 @@ static int sample_pass(shk_ctx *c, const uint64_t *words, uint32_t lo, uint32_t 
   const uint32_t stride = c->sample_stride > 1 ? c->sample_stride : 1;
   const uint32_t ns = (c->nregions + stride - 1) / stride;
   ShkMergeArgs A;
-  fill_args(c, &A, words, lo, hi, lo, 0, 0, 2);
-  A.newchunks = c->d_newchunks; A.chist = c->d_chist; A.rstride = stride;
+  fill_args(c, &A, words, lo, hi, 0);
+  A.want_hist = 1; A.newchunks = c->d_newchunks; A.chist = c->d_chist; A.rstride = stride;
   c->spill_valid = 0;
   c->chist_n = 0;
   HIPCHK(hipMemsetAsync(c->d_chist, 0, SHK_MAX_CHUNKS * 8, c->stream));
@@ -1143,27 +1090,15 @@ static int merge_stage_from(shk_ctx *c, const uint64_t *words, uint32_t nchunks,
     uint32_t hi = nchunks - 1;
     const bool watch = c->rounds_left > 0;
     MergeOut o;
-    uint32_t shift;
     int rc;
-    bool have_hist = false;
-    {
-      uint32_t span = hi - lo + 1;
-      shift = 0;
-      while ((span + (1u << shift) - 1) >> shift > SHK_HIST_BINS) shift++;
-    }
-    // a deNoise point inside this range is likely when the last range's rate of new keys would
-    // carry the distinct count past the trigger: then the statistics-only launch runs first
-    const bool likely = watch && c->new_frac > 0 &&
-                        (double)c->ndistinct + 0.8 * c->new_frac * (double)nwords * (double)(hi - lo + 1) / (double)nchunks >=
-                            (double)c->cfg.ndistinct_for_denoise;
-    // When the trigger is within reach of this batch the first launch also fills the first-chunk
-    // histogram, so that a pass which turns out to contain the deNoise point already yields its coarse position.
+    // When the trigger is within reach of this batch the summary launch also records the first chunk of every new key,
+    // so that a pass which turns out to contain the deNoise point already yields its exact position.
     // (with a known rate of new keys per k-mer, "within reach" means within twice the predicted gain; a
     // point that is missed this way only costs one more statistics pass)
     const double reach = c->new_frac > 0 ? 2.0 * c->new_frac * (double)nwords * (double)(hi - lo + 1) / (double)nchunks : (double)nwords;
     const bool possible = watch && (double)c->ndistinct + reach >= (double)c->cfg.ndistinct_for_denoise;
     int sv = 2;
-    if (possible && c->sample_stride > 1 && c->use_spill && !c->single_ok && !c->big_image && !c->counted) {
+    if (possible && c->sample_stride > 1 && !c->big_image && !c->counted) {
       // guess the chunk of the deNoise point from a sample of the regions and run the one-pass point with it; the pass
       // verifies the guess against the exact histogram it collects itself and, when it was wrong, is run once more
       uint32_t guess = 0;
@@ -1186,33 +1121,12 @@ static int merge_stage_from(shk_ctx *c, const uint64_t *words, uint32_t nchunks,
         // (anything else: the general path below)
       }
     }
-    if (c->single_ok && !likely) {
-      // single-launch scheme: one launch does statistics and table
-      rc = merge_single(c, words, lo, hi, 0, &o, possible ? 1 : 0, lo, shift);
-      have_hist = possible && !(o.err & ~soft);
-      if (rc) return rc;
-      if (o.err & ~(soft | SHK_E_HASH_FULL | SHK_E_LOOKBACK)) return map_err_bits(o.err & ~(soft | SHK_E_HASH_FULL | SHK_E_LOOKBACK));
-      const bool crosses = watch && c->ndistinct + o.newd >= c->cfg.ndistinct_for_denoise;
-      if (!o.err && !crosses) {
-        commit_single(c);
-        if (o.added) c->new_frac = (double)o.newd / (double)o.added;
-        c->ndistinct += o.newd; c->nelts += o.added;
-        st->kmers += o.added; st->new_distinct += o.newd; st->chunks += hi - lo + 1;
-        lo = hi + 1;
-        continue;
-      }
-      if (!crosses && (o.err & soft) && !(o.err & (SHK_E_HASH_FULL | SHK_E_LOOKBACK))) return map_err_bits(o.err);
-      // otherwise (deNoise point inside, hash overflow, or look-back gave up): the two-launch path below
-    }
+    const bool with_chist = possible && sv != 0;   // (sv == 0: the sample rules a point out)
+    bool have_chist = false;
     for (;;) {
-      if (have_hist) break;   // statistics of [lo, hi] are already known from the discarded single launch
-      uint32_t span = hi - lo + 1;
-      shift = 0;
-      while ((span + (1u << shift) - 1) >> shift > SHK_HIST_BINS) shift++;
-      const int wh = sv == 0 ? 0 : ((likely || (possible && c->use_spill)) ? 2 : 0);   // (sv == 0: the sample rules a point out)
-      rc = merge_summary(c, words, lo, hi, lo, shift, 0, &o, wh, 1);
+      rc = merge_summary(c, words, lo, hi, 0, &o, with_chist, true);
       if (rc) return rc;
-      if (wh && !(o.err & ~soft)) have_hist = true;
+      if (with_chist && !(o.err & ~soft)) have_chist = true;
       if (o.err & ~(soft | SHK_E_HASH_FULL)) return map_err_bits(o.err & ~(soft | SHK_E_HASH_FULL));
       if (o.err & SHK_E_HASH_FULL) {
         // more distinct new keys in one region than its LDS hash holds: take fewer chunks at once
@@ -1226,72 +1140,35 @@ static int merge_stage_from(shk_ctx *c, const uint64_t *words, uint32_t nchunks,
     if (watch && c->ndistinct + o.newd >= c->cfg.ndistinct_for_denoise) {
       // locate the first chunk at which the running distinct count reaches the trigger:
       // only now is the per-chunk histogram of first occurrences needed
-      uint32_t base = lo;
-      if (!have_hist) {
-        rc = merge_summary(c, words, lo, hi, lo, shift, 0, &o, 2);
+      if (!have_chist) {
+        rc = merge_summary(c, words, lo, hi, 0, &o, true, false);
         if (rc) return rc;
         if (o.err & ~soft) return map_err_bits(o.err & ~soft);
       }
-      if (o.have_chist) {
-        // exact: first chunk at which the running distinct count reaches the trigger
-        uint64_t run = c->ndistinct;
-        uint32_t ch = lo;
-        for (; ch < hi; ch++) {
-          run += c->h_chist[ch];
-          if (run >= c->cfg.ndistinct_for_denoise) break;
-        }
-        if (ch == hi) run += c->h_chist[ch];      // (the loop leaves the last chunk's keys out)
-        if (ch + 1 < nchunks) {
-          // the point lies inside the batch: everything -- the chunks up to it, the round, the chunks behind it -- in one pass
-          bool fused = false;
-          rc = denoise_fused(c, words, lo, ch, nchunks - 1, run - c->ndistinct, st, &fused);
-          if (rc) return rc;
-          if (fused) { lo = nchunks; continue; }
-        }
-        hi = ch;
-      } else
-      for (;;) {
-        uint32_t bin = 0;
-        uint64_t run = c->ndistinct + o.before;
-        for (bin = 0; bin < SHK_HIST_BINS; bin++) {
-          if (run + o.hist[bin] >= c->cfg.ndistinct_for_denoise) break;
-          run += o.hist[bin];
-        }
-        if (bin == SHK_HIST_BINS) bin = SHK_HIST_BINS - 1;  // cannot happen: the total crosses
-        uint32_t b_lo = base + (bin << shift);
-        uint32_t b_hi = b_lo + (1u << shift) - 1;
-        if (b_hi > hi) b_hi = hi;
-        if (shift == 0) { hi = b_lo; break; }
-        // refine inside [b_lo, b_hi]: keys first seen before b_lo are counted in `before`
-        uint32_t span2 = b_hi - b_lo + 1;
-        shift = 0;
-        while ((span2 + (1u << shift) - 1) >> shift > SHK_HIST_BINS) shift++;
-        base = b_lo;
-        rc = merge_summary(c, words, lo, b_hi, base, shift, 0, &o, 1);
-        if (rc) return rc;
-        if (o.err & ~soft) return map_err_bits(o.err & ~soft);
+      uint64_t run = c->ndistinct;
+      uint32_t ch = lo;
+      for (; ch < hi; ch++) {
+        run += c->h_chist[ch];
+        if (run >= c->cfg.ndistinct_for_denoise) break;
       }
+      if (ch == hi) run += c->h_chist[ch];      // (the loop leaves the last chunk's keys out)
+      if (ch + 1 < nchunks) {
+        // the point lies inside the batch: everything -- the chunks up to it, the round, the chunks behind it -- in one pass
+        bool fused = false;
+        rc = denoise_fused(c, words, lo, ch, nchunks - 1, run - c->ndistinct, st, &fused);
+        if (rc) return rc;
+        if (fused) { lo = nchunks; continue; }
+      }
+      hi = ch;
       fire = true;
       // rebuild for exactly the chunks [lo, hi]
-      bool written = false;
-      if (c->single_ok) {
-        rc = merge_single(c, words, lo, hi, 0, &o);
-        if (rc) return rc;
-        if (!o.err) { commit_single(c); written = true; }
-        else if (!(o.err & SHK_E_LOOKBACK)) return map_err_bits(o.err);
-      }
-      if (!written) {
-        rc = merge_summary(c, words, lo, hi, lo, 0, 0, &o, 0, 1);
-        if (rc) return rc;
-        if (o.err) return map_err_bits(o.err);
-        rc = merge_write(c, words, lo, hi, 0);
-        if (rc) return rc;
-      }
+      rc = merge_summary(c, words, lo, hi, 0, &o, false, true);
+      if (rc) return rc;
+      if (o.err) return map_err_bits(o.err);
+      rc = merge_write(c, words, lo, hi, 0);
+      if (rc) return rc;
     } else {
       if (o.err) return map_err_bits(o.err);
-      if (have_hist) {
-        // (only reached when the single launch was clean but is not committed: cannot happen without a crossing)
-      }
       rc = merge_write(c, words, lo, hi, 0);
       if (rc) return rc;
     }
@@ -1819,21 +1696,23 @@ extern "C" int shk_stage_words(shk_ctx *c, const uint64_t *d_words, uint64_t nwo
   return finish(c, rc);
 }
 
-extern "C" int shk_stage_summary(shk_ctx *c, uint32_t lo, uint32_t hi, uint32_t hist_base, uint32_t hist_shift,
-                                 int want_hist, shk_summary *out) {
+static void summary_out(const MergeOut &o, shk_summary *out) {
+  out->new_distinct = o.newd; out->added = o.added; out->removed = o.removed;
+  out->err_bits = o.err; out->reserved = 0;
+}
+
+extern "C" int shk_stage_summary(shk_ctx *c, uint32_t lo, uint32_t hi, int want_chunks, shk_summary *out) {
   if (!c || !out || hi < lo || hi >= SHK_MAX_CHUNKS) return SHK_ERR_ARG;
   HIPCHK(hipSetDevice(c->dev));
   MergeOut o;
-  int rc = merge_summary(c, c->d_words[c->staged], lo, hi, hist_base, hist_shift, 0, &o, want_hist, 1);
+  int rc = merge_summary(c, c->d_words[c->staged], lo, hi, 0, &o, want_chunks != 0, true);
   if (!rc && !c->big_image && (o.err & (SHK_E_OLD_EXTENT | SHK_E_NEW_EXTENT)) && !(o.err & SHK_E_TABLE_FULL)) {
     c->big_image = 1;   // a cluster outgrew the small LDS image: same range with the big one
-    rc = merge_summary(c, c->d_words[c->staged], lo, hi, hist_base, hist_shift, 0, &o, want_hist, 1);
+    rc = merge_summary(c, c->d_words[c->staged], lo, hi, 0, &o, want_chunks != 0, true);
   }
   prof_collect(c);
   if (rc) return rc;
-  out->new_distinct = o.newd; out->added = o.added; out->removed = o.removed; out->before = o.before;
-  for (int i = 0; i < SHK_HIST_BINS; i++) out->hist[i] = o.hist[i];
-  out->err_bits = o.err; out->reserved = 0;
+  summary_out(o, out);
   return SHK_OK;
 }
 
@@ -1846,26 +1725,19 @@ extern "C" int shk_stage_commit(shk_ctx *c, uint32_t lo, uint32_t hi, const shk_
   return finish(c, rc);
 }
 
-extern "C" int shk_stage_try(shk_ctx *c, uint32_t lo, uint32_t hi, uint32_t hist_base, uint32_t hist_shift, int want_hist,
-                             shk_summary *out) {
+extern "C" int shk_stage_try(shk_ctx *c, uint32_t lo, uint32_t hi, int want_chunks, shk_summary *out) {
   if (!c || !out || hi < lo || hi >= SHK_MAX_CHUNKS) return SHK_ERR_ARG;
   HIPCHK(hipSetDevice(c->dev));
   MergeOut o;
   int rc;
   for (int attempt = 0; attempt < 2; attempt++) {
-    if (c->single_ok) rc = merge_single(c, c->d_words[c->staged], lo, hi, 0, &o, want_hist, hist_base, hist_shift);
-    else {
-      rc = merge_summary(c, c->d_words[c->staged], lo, hi, hist_base, hist_shift, 0, &o, want_hist, 1);
-      if (!c->use_spill) o.err |= SHK_E_LOOKBACK;   // plain two-launch scheme: the caller commits through shk_stage_commit
-    }
+    rc = merge_summary(c, c->d_words[c->staged], lo, hi, 0, &o, want_chunks != 0, true);
     if (rc || c->big_image || !(o.err & (SHK_E_OLD_EXTENT | SHK_E_NEW_EXTENT)) || (o.err & SHK_E_TABLE_FULL)) break;
     c->big_image = 1;
   }
   prof_collect(c);
   if (rc) return rc;
-  out->new_distinct = o.newd; out->added = o.added; out->removed = o.removed; out->before = o.before;
-  for (int i = 0; i < SHK_HIST_BINS; i++) out->hist[i] = o.hist[i];
-  out->err_bits = o.err; out->reserved = 0;
+  summary_out(o, out);
   return SHK_OK;
 }
 
@@ -1873,14 +1745,11 @@ extern "C" int shk_stage_accept(shk_ctx *c, const shk_summary *s) {
   if (!c || !s) return SHK_ERR_ARG;
   if (s->err_bits) return map_err_bits(s->err_bits);
   HIPCHK(hipSetDevice(c->dev));
-  if (c->single_ok) commit_single(c);
-  else {
-    if (!c->spill_valid) return SHK_ERR_ARG;   // nothing was tried
-    const int dn = c->spill_denoise;
-    int rc = merge_write(c, c->spill_words, c->spill_lo, c->spill_hi, dn);
-    if (rc) return finish(c, rc);
-    if (dn) { c->big_image = 0; c->rounds_done++; }
-  }
+  if (!c->spill_valid) return SHK_ERR_ARG;   // nothing was tried
+  const int dn = c->spill_denoise;
+  int rc = merge_write(c, c->spill_words, c->spill_lo, c->spill_hi, dn);
+  if (rc) return finish(c, rc);
+  if (dn) { c->big_image = 0; c->rounds_done++; }
   c->ndistinct += s->new_distinct; c->nelts += s->added;
   c->ndistinct -= s->removed; c->nelts -= s->removed;     // (only a deNoise try removes anything)
   return finish(c, SHK_OK);
@@ -1888,26 +1757,19 @@ extern "C" int shk_stage_accept(shk_ctx *c, const shk_summary *s) {
 
 // deNoise round on this shard fused with the insertion of the staged chunks [lo, hi] (the chunks behind the deNoise
 // point): marks + statistics pass; nothing is written until shk_stage_accept. s->removed = singletons dropped,
-// s->new_distinct counts dropped keys that reappear in [lo, hi] as new. Needs the spill scheme (default).
+// s->new_distinct counts dropped keys that reappear in [lo, hi] as new.
 extern "C" int shk_stage_try_denoise(shk_ctx *c, uint32_t lo, uint32_t hi, shk_summary *out) {
   if (!c || !out || hi < lo || hi >= SHK_MAX_CHUNKS) return SHK_ERR_ARG;
-  if (!c->use_spill) {        // (another rebuild scheme was asked for: the caller runs shk_denoise and goes on)
-    memset(out, 0, sizeof(*out));
-    out->err_bits = SHK_E_FUSED;
-    return SHK_OK;
-  }
   HIPCHK(hipSetDevice(c->dev));
   uint64_t ml = c->cfg.min_denoise_len ? c->cfg.min_denoise_len : (1ULL << 20);
   { ProfScope ps(c, KP_MARKS);
     hipLaunchKernelGGL(k_denoise_marks, dim3(1), dim3(64), 0, c->stream, c->tab[c->cur], c->nslots, c->xnslots, c->nblocks,
                        ml, (unsigned long long *)(c->d_scalars + 3)); }
   MergeOut o;
-  int rc = merge_summary(c, c->d_words[c->staged], lo, hi, lo, 0, 1, &o, 0, 1);
+  int rc = merge_summary(c, c->d_words[c->staged], lo, hi, 1, &o, false, true);
   prof_collect(c);
   if (rc) return rc;
-  out->new_distinct = o.newd; out->added = o.added; out->removed = o.removed; out->before = o.before;
-  for (int i = 0; i < SHK_HIST_BINS; i++) out->hist[i] = o.hist[i];
-  out->err_bits = o.err; out->reserved = 0;
+  summary_out(o, out);
   return SHK_OK;
 }
 
@@ -1936,8 +1798,8 @@ extern "C" int shk_stage_point_try(shk_ctx *c, uint32_t lo, uint32_t split, uint
   HIPCHK(hipSetDevice(c->dev));
   c->pt_valid = 0;
   memset(out, 0, sizeof(*out));
-  // (needs the spill scheme; the retry image is not instantiated for this pass: the caller takes another path)
-  if (c->big_image || !c->use_spill || c->single_ok) { out->err_bits = SHK_E_FUSED; return SHK_OK; }
+  // (the retry image is not instantiated for this pass: the caller takes another path)
+  if (c->big_image) { out->err_bits = SHK_E_FUSED; return SHK_OK; }
   PointOut po;
   int rc = point_try(c, c->d_words[c->staged], lo, split, hi, true, &po);
   prof_collect(c);
@@ -1954,8 +1816,8 @@ extern "C" int shk_stage_round_try(shk_ctx *c, shk_point *out) {
   HIPCHK(hipSetDevice(c->dev));
   c->pt_valid = 0;
   memset(out, 0, sizeof(*out));
-  // (needs the spill scheme; the retry image is not instantiated for this pass: the caller takes another path)
-  if (c->big_image || !c->use_spill || c->single_ok) { out->err_bits = SHK_E_FUSED; return SHK_OK; }
+  // (the retry image is not instantiated for this pass: the caller takes another path)
+  if (c->big_image) { out->err_bits = SHK_E_FUSED; return SHK_OK; }
   PointOut po;
   int rc = point_try(c, nullptr, 0, 0, 0, false, &po);
   prof_collect(c);
@@ -2130,7 +1992,7 @@ extern "C" int shk_lookup(shk_ctx *c, const uint64_t *keys, uint64_t n, int on_d
 // rebuild with the words of a counted insert; nothing is committed unless the pass is clean
 static int merge_plain(shk_ctx *c, const uint64_t *words, MergeOut *o) {
   for (int attempt = 0; attempt < 2; attempt++) {
-    int rc = merge_summary(c, words, 0, SHK_MAX_CHUNKS - 1, 0, 0, 0, o, 0, 1);
+    int rc = merge_summary(c, words, 0, SHK_MAX_CHUNKS - 1, 0, o, false, true);
     if (rc) return rc;
     if (!c->big_image && (o->err & (SHK_E_OLD_EXTENT | SHK_E_NEW_EXTENT)) && !(o->err & SHK_E_TABLE_FULL)) { c->big_image = 1; continue; }
     break;
@@ -2225,9 +2087,9 @@ extern "C" int shk_dump(shk_ctx *c, uint64_t *keys, uint64_t *counts, uint64_t c
   if (!c || !n_out || (keys && !counts)) return SHK_ERR_ARG;
   HIPCHK(hipSetDevice(c->dev));
   ShkMergeArgs A;
-  fill_args(c, &A, nullptr, 0, 0, 0, 0, 0);
+  fill_args(c, &A, nullptr, 0, 0, 0);
   uint32_t *nper = c->d_over_list;                       // scratch of the spill scheme: [nregions + 1]
-  uint64_t *offs = (uint64_t *)c->d_lb_agg;              // [nregions + 2]
+  uint64_t *offs = c->d_dump_offs;                       // [nregions + 2]
   unsigned long long *stop = (unsigned long long *)(c->d_scalars + 5);
   const uint64_t *no_offs = nullptr;
   uint64_t *no_out = nullptr;
@@ -2280,8 +2142,8 @@ static int merge2_run(shk_ctx *c, const ShkSrc2 &S, uint64_t *newd_out, uint64_t
   ShkMergeArgs A;
   uint64_t newd = 0, added = 0;
   for (int attempt = 0; attempt < 2; attempt++) {
-    fill_args(c, &A, nullptr, 0, 0, 0, 0, 0);
-    HIPCHK(hipMemsetAsync(c->d_counters, 0, (4 + SHK_HIST_BINS + 1) * 8, c->stream));
+    fill_args(c, &A, nullptr, 0, 0, 0);
+    HIPCHK(hipMemsetAsync(c->d_counters, 0, (SHK_CNT_NOVER + 1) * 8, c->stream));
     c->spill_valid = 0;
     { ProfScope ps(c, KP_MERGE_SUM);
       SHK_FOR_REGION_SLICES(c, A, nblk) {

@@ -27,7 +27,6 @@
 #define SHK_MERGE_GROUP 128                            // ... helped by one more wave while staging and folding the batch keys (the kernel is bound by instruction issue: more helpers only add instructions)
 #define SHK_CHUNK_BITS 12                              // chunk index field of a key word
 #define SHK_MAX_CHUNKS (1u << SHK_CHUNK_BITS)
-#define SHK_HIST_BINS 32
 
 // error bits raised by kernels (ctx->d_err), reported through the C ABI
 #define SHK_E_OLD_EXTENT   (1u << 0)   // a region's old runs spill further than the LDS image
@@ -38,7 +37,7 @@
 #define SHK_E_BAD_FASTQ    (1u << 5)   // read longer than 65535 / k out of range
 #define SHK_E_KEYS_FULL    (1u << 6)   // batch produced more keys than the key buffer holds
 #define SHK_E_RUN_TOO_LONG (1u << 7)
-#define SHK_E_LOOKBACK     (1u << 8)   // single-launch rebuild gave up waiting for a predecessor (host falls back)
+                                       // (bit 8 is free: the flags keep their numbers, shk/__init__.py hard-codes some)
 #define SHK_E_FUSED        (1u << 9)   // the one-pass deNoise point met a region it does not handle (host takes the three-pass path)
 #define SHK_E_SLOT_FULL    (1u << 10)  // last partition level with fixed-capacity region slots: a region got more words (host redoes the level with exact bases)
 

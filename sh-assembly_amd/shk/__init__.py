@@ -38,8 +38,8 @@ class Totals(C.Structure):
 
 
 class Summary(C.Structure):
-    _fields_ = [("new_distinct", C.c_uint64), ("added", C.c_uint64), ("removed", C.c_uint64), ("before", C.c_uint64),
-                ("hist", C.c_uint64 * 32), ("err_bits", C.c_uint32), ("reserved", C.c_uint32)]
+    _fields_ = [("new_distinct", C.c_uint64), ("added", C.c_uint64), ("removed", C.c_uint64),
+                ("err_bits", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class Point(C.Structure):
@@ -50,8 +50,6 @@ class Point(C.Structure):
 
 SOFT_BITS = 0x0A
 HASH_FULL_BIT = 0x04
-LOOKBACK_BIT = 0x100
-HIST_BINS = 32
 
 
 class KernelTime(C.Structure):
@@ -93,9 +91,9 @@ def load(path=None):
     L.shk_count_words.argtypes = [vp, vp, u64, u32, C.POINTER(BatchStats)]
     L.shk_route_words.argtypes = [vp, u64, u32, C.POINTER(vp), pu64]
     L.shk_stage_words.argtypes = [vp, vp, u64]
-    L.shk_stage_summary.argtypes = [vp, u32, u32, u32, u32, i32, C.POINTER(Summary)]
+    L.shk_stage_summary.argtypes = [vp, u32, u32, i32, C.POINTER(Summary)]
     L.shk_stage_commit.argtypes = [vp, u32, u32, C.POINTER(Summary)]
-    L.shk_stage_try.argtypes = [vp, u32, u32, u32, u32, i32, C.POINTER(Summary)]
+    L.shk_stage_try.argtypes = [vp, u32, u32, i32, C.POINTER(Summary)]
     L.shk_stage_accept.argtypes = [vp, C.POINTER(Summary)]
     L.shk_stage_try_denoise.argtypes = [vp, u32, u32, C.POINTER(Summary)]
     L.shk_stage_chunk_hist.argtypes = [vp, C.POINTER(u64), u32]
@@ -329,18 +327,18 @@ class Context:
     def stage_words(self, d_words, nwords):
         self._chk(self.L.shk_stage_words(self.h, C.c_void_p(int(d_words) if d_words else 0), nwords))
 
-    def stage_summary(self, lo, hi, hist_base=0, hist_shift=0, want_hist=False):
+    def stage_summary(self, lo, hi, want_chunks=False):
         s = Summary()
-        self._chk(self.L.shk_stage_summary(self.h, lo, hi, hist_base, hist_shift, int(want_hist), C.byref(s)))
+        self._chk(self.L.shk_stage_summary(self.h, lo, hi, int(want_chunks), C.byref(s)))
         return s
 
-    def stage_try(self, lo, hi, hist_base=0, hist_shift=0, want_hist=False):
+    def stage_try(self, lo, hi, want_chunks=False):
         s = Summary()
-        self._chk(self.L.shk_stage_try(self.h, lo, hi, hist_base, hist_shift, int(want_hist), C.byref(s)))
+        self._chk(self.L.shk_stage_try(self.h, lo, hi, int(want_chunks), C.byref(s)))
         return s
 
     def stage_chunk_hist(self, n):
-        """exact per-chunk histogram of the last pass run with want_hist=2, or None when it has none"""
+        """exact per-chunk histogram of the last pass run with want_chunks, or None when it has none"""
         out = (C.c_uint64 * max(n, 1))()
         if self.L.shk_stage_chunk_hist(self.h, out, n) != 0:
             return None

@@ -16,7 +16,7 @@ import os
 import torch
 import torch.distributed as dist
 
-from . import HASH_FULL_BIT, HIST_BINS, LOOKBACK_BIT, SOFT_BITS, ShkError, Summary
+from . import HASH_FULL_BIT, SOFT_BITS, ShkError, Summary
 
 NBITS = 10       # kernel flag bits (csrc/shk_device.h SHK_E_*)
 NCODES = 8       # SHK_ERR_* codes -1 .. -8 (include/shk.h)
@@ -68,15 +68,15 @@ def _local(st, call, default=None):
 
 class _Decision:
     """statistics of one try/summary on every rank, reduced: sums of the counters, OR of the flag bits"""
-    __slots__ = ("newd", "before", "added", "removed", "hist", "chist", "bits", "local")
+    __slots__ = ("newd", "added", "removed", "chist", "bits", "local")
 
     @property
     def hard(self):
-        return self.bits & ~(SOFT_BITS | HASH_FULL_BIT | LOOKBACK_BIT) & 0xFFFFFFFF
+        return self.bits & ~(SOFT_BITS | HASH_FULL_BIT) & 0xFFFFFFFF
 
     @property
     def hfull(self):
-        return self.bits & (HASH_FULL_BIT | LOOKBACK_BIT)
+        return self.bits & HASH_FULL_BIT
 
     @property
     def soft(self):
@@ -90,7 +90,7 @@ def _decide(ctx, st, call, chist_range=None, extra=None):
     s = _local(st, call, None)
     if s is None:
         s = Summary()
-    vec = [s.new_distinct, s.before, s.added, s.removed] + list(s.hist)
+    vec = [s.new_distinct, s.added, s.removed]
     vec += [(s.err_bits >> b) & 1 for b in range(NBITS)]
     vec += [1 if st.pending_rc == -c else 0 for c in range(1, NCODES + 1)]
     nch = 0
@@ -102,19 +102,18 @@ def _decide(ctx, st, call, chist_range=None, extra=None):
     if extra:
         vec += list(extra)
     red = _allreduce(vec, st)
-    codes = red[4 + HIST_BINS + NBITS: 4 + HIST_BINS + NBITS + NCODES]
+    codes = red[3 + NBITS: 3 + NBITS + NCODES]
     for c in range(1, NCODES + 1):
         if codes[c - 1]:
             st.pending_rc = 0
             raise ShkError(-c, "%s (on %d of the ranks)" % (ctx.L.shk_strerror(-c).decode(), codes[c - 1]))
     d = _Decision()
-    d.newd, d.before, d.added, d.removed = red[0:4]
-    d.hist = red[4:4 + HIST_BINS]
-    d.bits = sum(1 << b for b in range(NBITS) if red[4 + HIST_BINS + b])
+    d.newd, d.added, d.removed = red[0:3]
+    d.bits = sum(1 << b for b in range(NBITS) if red[3 + b])
     d.local = s
     d.chist = None
     if chist_range is not None:
-        base = 4 + HIST_BINS + NBITS + NCODES
+        base = 3 + NBITS + NCODES
         if red[base] == dist.get_world_size():
             d.chist = red[base + 1: base + 1 + nch]
     return d
@@ -328,11 +327,11 @@ def sharded_count(ctx, st, nchunks):
                     if _one_pass_point(ctx, st, lo, r, nchunks - 1, out) == "done":
                         lo = nchunks
                         continue
-        # common case: one try per rank does statistics (and, in the single-launch scheme, the table); accepted when
-        # no rank saw an error and the whole filter stays below the trigger. While rounds are left the try also
-        # records first chunks and their histogram rides along, so a deNoise point is located without more passes.
+        # common case: one try per rank does statistics; accepted when no rank saw an error and the whole filter stays
+        # below the trigger. While rounds are left the try also records first chunks and their histogram rides along,
+        # so a deNoise point is located without more passes.
         wh = watch and verdict != 0      # (verdict 0: the sample rules a point out; should it be wrong the summary below is redone)
-        d = _decide(ctx, st, lambda: ctx.stage_try(lo, hi, lo, 0, 2 if wh else 0), (lo, hi) if wh else None)
+        d = _decide(ctx, st, lambda: ctx.stage_try(lo, hi, wh), (lo, hi) if wh else None)
         if d.hard:
             fail(d)
         crosses = watch and st.ndistinct + d.newd >= st.trigger
@@ -342,14 +341,9 @@ def sharded_count(ctx, st, nchunks):
             lo = hi + 1
             continue
         point = _point(st, d, lo, hi) if (crosses and not d.hfull and d.chist is not None) else None
-        shift = 0
         if point is None:
             while True:
-                span = hi - lo + 1
-                shift = 0
-                while ((span + (1 << shift) - 1) >> shift) > HIST_BINS:
-                    shift += 1
-                d = _decide(ctx, st, lambda: ctx.stage_summary(lo, hi, lo, shift, 2 if watch else 0), (lo, hi) if watch else None)
+                d = _decide(ctx, st, lambda: ctx.stage_summary(lo, hi, watch), (lo, hi) if watch else None)
                 if d.hard:
                     fail(d)
                 if d.hfull:
@@ -369,43 +363,18 @@ def sharded_count(ctx, st, nchunks):
         fire = False
         accepted = False
         if crosses:
-            if point is not None:
-                hi = point
-            else:
-                # 32-bin refinement (contexts without the exact histogram)
-                base = lo
-                d = _decide(ctx, st, lambda: ctx.stage_summary(lo, hi, lo, shift, True))
-                if d.hard:
-                    fail(d)
-                while True:
-                    run = st.ndistinct + d.before
-                    b = 0
-                    while b < HIST_BINS:
-                        if run + d.hist[b] >= st.trigger:
-                            break
-                        run += d.hist[b]
-                        b += 1
-                    b = min(b, HIST_BINS - 1)
-                    b_lo = base + (b << shift)
-                    b_hi = min(b_lo + (1 << shift) - 1, hi)
-                    if shift == 0:
-                        hi = b_lo
-                        break
-                    span2 = b_hi - b_lo + 1
-                    shift = 0
-                    while ((span2 + (1 << shift) - 1) >> shift) > HIST_BINS:
-                        shift += 1
-                    base = b_lo
-                    d = _decide(ctx, st, lambda: ctx.stage_summary(lo, b_hi, base, shift, True))
-                    if d.hard:
-                        fail(d)
+            if point is None:
+                # every rank records first chunks while rounds are left: a missing histogram means a rank failed
+                check(ctx, st)
+                raise ShkError(-5, "deNoise point without the first-chunk histogram")
+            hi = point
             fire = True
-            d = _decide(ctx, st, lambda: ctx.stage_try(lo, hi, lo, 0, 0))
+            d = _decide(ctx, st, lambda: ctx.stage_try(lo, hi))
             if not (d.hard or d.hfull or d.soft):
                 _local(st, lambda: ctx.stage_accept(d.local))
                 accepted = True
             else:
-                d = _decide(ctx, st, lambda: ctx.stage_summary(lo, hi, lo, 0, 0))
+                d = _decide(ctx, st, lambda: ctx.stage_summary(lo, hi))
         if d.hard or d.hfull or d.soft:
             fail(d)
         if not accepted:

@@ -65,11 +65,11 @@ def main():
         # sampled location of the deNoise point (read at context creation): off, or every 2nd / 4th / 8th region -- on these
         # small tables the guess is often wrong, which is the point
         os.environ["SHK_SAMPLE_STRIDE"] = str(rnd.choice([0, 2, 2, 4, 8]))
-        # the rebuild schemes behind the default one (fallbacks and diagnostics) must stay byte-exact too: the library reads
-        # these switches when a context is created / a pass is planned
-        for v in ("SHK_SINGLE", "SHK_TWO_LAUNCH", "SHK_COARSE_HIST", "SHK_NO_FUSED_POINT", "SHK_RP_NO_GROUPS"):
+        # the fallbacks behind the default path must stay byte-exact too: the library reads these switches when a
+        # context is created / a pass is planned
+        for v in ("SHK_NO_FUSED_POINT", "SHK_RP_NO_GROUPS"):
             os.environ.pop(v, None)
-        scheme = rnd.choice([None] * 5 + ["SHK_SINGLE", "SHK_TWO_LAUNCH", "SHK_COARSE_HIST", "SHK_NO_FUSED_POINT", "SHK_RP_NO_GROUPS"])
+        scheme = rnd.choice([None] * 2 + ["SHK_NO_FUSED_POINT", "SHK_RP_NO_GROUPS"])
         if scheme:
             os.environ[scheme] = "1"
         if args.sharded:
