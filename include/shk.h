@@ -305,7 +305,7 @@ int shk_lookup(shk_ctx *ctx, const uint64_t *keys, uint64_t n, int on_device, in
  * max_ext appended bases and the filter counts of the k-mers they complete, out_n their number, out_stop why
  * the walk ended (SHK_STOP_*), out_branch (may be NULL) at a SHK_STOP_BRANCH the solid neighbours of the last
  * k-mer s0 s1..s(k-1): bit x = successor s1..s(k-1)+x, bit 4+z = sibling z+s1..s(k-1) (x, z index "ACGT"); out_ncount (may be NULL, 8 per end) their filter counts. mark_traveled != 0 sets the traveled bit of every k-mer looked up, as the
- * reference's count_key_value_set_traveled does. k <= 64. All pointers are host pointers. */
+ * reference's count_key_value_set_traveled does. 2 <= k <= 191. All pointers are host pointers. */
 #define SHK_STOP_BRANCH 1
 #define SHK_STOP_DEAD_END 2
 #define SHK_STOP_CIRCLE 3
@@ -317,7 +317,7 @@ int shk_extend_forward(shk_ctx *ctx, const char *cur_kmers, const char *first_km
                        uint32_t *out_ncount);
 /* One maximal unitig per seed k-mer: extend, reverse-complement, extend again; out_seq[i*max_len ..] holds
  * out_len[i] bases, out_median[i] the contig's median abundance as the reference stores it (int),
- * out_stop[2*i], out_stop[2*i+1] the two stop reasons. seed_counts[i] = the seed's filter count. */
+ * out_stop[2*i], out_stop[2*i+1] the two stop reasons. seed_counts[i] = the seed's filter count. 2 <= k <= 191. */
 int shk_unitigs_from_seeds(shk_ctx *ctx, const char *seeds, const uint32_t *seed_counts, uint32_t n, uint32_t k,
                            uint64_t abundance_min, uint32_t max_len, char *out_seq, uint32_t *out_len,
                            int32_t *out_median, uint8_t *out_stop);
@@ -327,7 +327,8 @@ int shk_unitigs_from_seeds(shk_ctx *ctx, const char *seeds, const uint32_t *seed
  * in T,G,C,A order, src/contig_assembly.cpp:606-626, 1012-1084): seeds are extended in both directions, every solid
  * neighbour met at a branch starts a new contig (the reference's work queue), a unitig found more than once is
  * kept once. The reference produces the same set of sequences up to reverse complement; ids and order are its
- * thread schedule's and are not reproduced. */
+ * thread schedule's and are not reproduced. 2 <= k <= 191 here and in the unitig set's calls below; the device holds a
+ * k-mer in 2, 4 or 6 64-bit words (k <= 64, 128, 191), so k <= 64 costs what it always did. */
 typedef struct shk_unitig_stats {
   uint64_t unitigs, total_len;   /* kept unitigs and their summed length */
   uint64_t rounds, extensions;   /* launches of the walk kernel; bases appended by all walks (duplicates included) */
@@ -338,7 +339,8 @@ int shk_find_unitigs(shk_ctx *ctx, const char *seeds, const uint32_t *seed_count
 /* The same in pieces, for callers that feed seeds batch by batch (the Contiger command line): a unitig set that
  * accumulates over calls. With mark_traveled != 0 every k-mer an extension looks up is marked, so that
  * shk_select_seeds(use_traveled = 1) on later reads skips seeds inside unitigs that are already known -- the
- * reference's own pruning (contig_assembly.cpp:1871-1873). */
+ * reference's own pruning (contig_assembly.cpp:1871-1873). A set keeps the k of its first call: a later call with
+ * another k returns SHK_ERR_ARG. */
 typedef struct shk_unitig_set shk_unitig_set;
 shk_unitig_set *shk_unitig_set_new(void);
 void shk_unitig_set_free(shk_unitig_set *u);
@@ -354,7 +356,7 @@ int shk_unitigs_add_reads(shk_ctx *ctx, shk_unitig_set *u, const void *text, int
 /* Seeds of the reads in the given FASTQ chunks (processDataChunk, contig_assembly.cpp:1856-1876): the k-mer at
  * len/2 - k/2 of every read, upper-cased, without 'N', whose filter count lies in [count_min, count_max]; with
  * use_traveled != 0 the lookup marks the k-mer and a k-mer that was already marked gives no seed. out_seeds
- * receives *n_out * k bases (capacity cap seeds), out_counts their counts. */
+ * receives *n_out * k bases (capacity cap seeds), out_counts their counts. 2 <= k <= 191. */
 int shk_select_seeds(shk_ctx *ctx, const void *text, int text_on_device, uint64_t text_bytes, const uint64_t *chunk_off,
                      const uint64_t *chunk_len, uint32_t nchunks, uint32_t k, uint64_t count_min, uint64_t count_max,
                      int use_traveled, char *out_seeds, uint32_t *out_counts, uint32_t cap, uint32_t *n_out);

@@ -2293,6 +2293,16 @@ extern "C" int shk_select_seeds(shk_ctx *c, const void *text, int text_on_device
 }
 
 // ------------------------------------------------------------------ Contiger: unitig extension (first slice)
+// The Contiger kernels that hold k-mers are instantiated for W = 2, 4, 6 words per k-mer (shk_walk_words(k)): the
+// statement runs with the constexpr KW set to the instantiation's W
+#define SHK_BY_WORDS(w, ...) do {                                  \
+    switch (w) {                                                   \
+      case 2: { constexpr int KW = 2; __VA_ARGS__; } break;        \
+      case 4: { constexpr int KW = 4; __VA_ARGS__; } break;        \
+      default: { constexpr int KW = 6; __VA_ARGS__; } break;       \
+    }                                                              \
+  } while (0)
+
 extern "C" int shk_extend_forward(shk_ctx *c, const char *cur_kmers, const char *first_kmers, uint32_t n, uint32_t k,
                                   uint64_t abundance_min, int mark_traveled, uint32_t max_ext, char *out_bases,
                                   uint32_t *out_counts, uint32_t *out_n, uint8_t *out_stop, uint8_t *out_branch,
@@ -2318,8 +2328,9 @@ extern "C" int shk_extend_forward(shk_ctx *c, const char *cur_kmers, const char 
     char *dk = w.dk, *df = w.df, *db = w.db;          // (plain pointers: the launch must not capture the owning struct)
     uint32_t *dc = w.dc, *dn = w.dn, *dnc = w.dnc;
     uint8_t *ds = w.ds, *dbr = w.dbr;
-    hipLaunchKernelGGL(k_extend_forward, dim3((n + 63) / 64), dim3(64), 0, c->stream, c->tab[c->cur], c->q_lo, c->nslots,
-                       c->cfg.hb, dk, df, n, k, abundance_min, mark_traveled ? 1 : 2, max_ext, db, dc, dn, ds, dbr, dnc); }
+    SHK_BY_WORDS(shk_walk_words(k),
+      hipLaunchKernelGGL(k_extend_forward<KW>, dim3((n + 63) / 64), dim3(64), 0, c->stream, c->tab[c->cur], c->q_lo, c->nslots,
+                         c->cfg.hb, dk, df, n, k, abundance_min, mark_traveled ? 1 : 2, max_ext, db, dc, dn, ds, dbr, dnc)); }
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(out_bases, w.db, ne, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipMemcpyAsync(out_counts, w.dc, ne * 4, hipMemcpyDeviceToHost, c->stream));
@@ -2410,20 +2421,24 @@ struct shk_unitig_set {
   char *d_seeds = nullptr; uint32_t *d_counts = nullptr; uint64_t seeds_cap = 0;
   uint32_t ncontigs = 1;                               // next free id (the reference starts with contigs.resize(1))
   uint32_t k = 0, max_len = 0;
+  uint32_t W = 0;                                      // words per packed k-mer (shk_walk_words(k)): planes per k-mer array and map key
   uint64_t amin = 0;
   shk_unitig_stats st;
   shk_unitig_set() { memset(&st, 0, sizeof(st)); memset(&G, 0, sizeof(G)); }
 };
 extern "C" shk_unitig_set *shk_unitig_set_new(void) { return new shk_unitig_set(); }
+// every device array of a set's ShkUG (unallocated planes are null)
+static void ug_free_arrays(ShkUG &G) {
+  for (int j = 0; j < SHK_KM_WMAX; j++) { hipFree(G.first[j]); hipFree(G.cur[j]); hipFree(G.rc[j]); hipFree(G.mk[j]); }
+  hipFree(G.fh); hipFree(G.rh); hipFree(G.hmin); hipFree(G.len); hipFree(G.l1); hipFree(G.cnt0); hipFree(G.state); hipFree(G.kind);
+  hipFree(G.stop); hipFree(G.mv); hipFree(G.ck); hipFree(G.cv);
+}
 extern "C" void shk_unitig_set_free(shk_unitig_set *u) {
   if (!u) return;
   if (u->c) {
     hipSetDevice(u->c->dev);
     hipStreamSynchronize(u->c->stream);
-    ShkUG &G = u->G;
-    hipFree(G.first_lo); hipFree(G.first_hi); hipFree(G.cur_lo); hipFree(G.cur_hi); hipFree(G.rc_lo); hipFree(G.rc_hi);
-    hipFree(G.fh); hipFree(G.rh); hipFree(G.hmin); hipFree(G.len); hipFree(G.l1); hipFree(G.cnt0); hipFree(G.state); hipFree(G.kind);
-    hipFree(G.stop); hipFree(G.mk_lo); hipFree(G.mk_hi); hipFree(G.mv); hipFree(G.ck); hipFree(G.cv);
+    ug_free_arrays(u->G);
     hipFree(u->d_list[0]); hipFree(u->d_list[1]); hipFree(u->d_scal); hipFree(u->d_stats); hipFree(u->d_seeds); hipFree(u->d_counts);
     if (u->h_scal) hipHostFree(u->h_scal);
   }
@@ -2439,9 +2454,10 @@ static int ug_reserve(shk_unitig_set *u, uint64_t ncontigs_after, uint64_t nlist
     while (nc < ncontigs_after + 1) nc *= 2;
     if (nc > 0x7FFFFFF0ull) return SHK_ERR_BATCH;
     const uint64_t o = u->cap;
-    if (ug_grow(&G.first_lo, o, nc, c->stream, false) || ug_grow(&G.first_hi, o, nc, c->stream, false) || ug_grow(&G.cur_lo, o, nc, c->stream, false) ||
-        ug_grow(&G.cur_hi, o, nc, c->stream, false) || ug_grow(&G.rc_lo, o, nc, c->stream, false) || ug_grow(&G.rc_hi, o, nc, c->stream, false) ||
-        ug_grow(&G.fh, o, nc, c->stream, false) || ug_grow(&G.rh, o, nc, c->stream, false) || ug_grow(&G.hmin, o, nc, c->stream, false) ||
+    for (uint32_t j = 0; j < u->W; j++)
+      if (ug_grow(&G.first[j], o, nc, c->stream, false) || ug_grow(&G.cur[j], o, nc, c->stream, false) || ug_grow(&G.rc[j], o, nc, c->stream, false))
+        return SHK_ERR_HIP;
+    if (ug_grow(&G.fh, o, nc, c->stream, false) || ug_grow(&G.rh, o, nc, c->stream, false) || ug_grow(&G.hmin, o, nc, c->stream, false) ||
         ug_grow(&G.len, o, nc, c->stream, true) || ug_grow(&G.l1, o, nc, c->stream, true) || ug_grow(&G.cnt0, o, nc, c->stream, true) ||
         ug_grow(&G.state, o, nc, c->stream, true) || ug_grow(&G.kind, o, nc, c->stream, true) || ug_grow(&G.stop, o, nc, c->stream, true))
       return SHK_ERR_HIP;
@@ -2458,17 +2474,24 @@ static int ug_reserve(shk_unitig_set *u, uint64_t ncontigs_after, uint64_t nlist
     uint64_t nm = u->mcap ? u->mcap : 4096;
     while (nm < ncontigs_after * 8) nm *= 2;
     if (nm > 0x80000000ull) return SHK_ERR_BATCH;
-    uint64_t *ok_lo = G.mk_lo, *ok_hi = G.mk_hi; uint32_t *ov = G.mv;
+    const ShkUG old = G;                      // (its mk / mv: the table being replaced)
     const uint32_t ocap = u->mcap;
-    G.mk_lo = G.mk_hi = nullptr; G.mv = nullptr;
-    if (dmalloc(&G.mk_lo, nm) || dmalloc(&G.mk_hi, nm) || dmalloc(&G.mv, nm)) return SHK_ERR_HIP;
-    HIPCHK(hipMemsetAsync(G.mv, 0, nm * 4, c->stream));
-    G.mmask = (uint32_t)(nm - 1); u->mcap = (uint32_t)nm;
-    if (ocap) {
-      hipLaunchKernelGGL(k_ug_rehash, dim3((ocap + 255) / 256), dim3(256), 0, c->stream, G, (const uint64_t *)ok_lo, (const uint64_t *)ok_hi, (const uint32_t *)ov, ocap);
-      HIPCHK(hipStreamSynchronize(c->stream));
-      hipFree(ok_lo); hipFree(ok_hi); hipFree(ov);
+    for (int j = 0; j < SHK_KM_WMAX; j++) G.mk[j] = nullptr;
+    G.mv = nullptr;
+    // (a failure here leaves the old table with `old` and the new planes in G: both released below / by the caller)
+    int rc = dmalloc(&G.mv, nm) ? SHK_ERR_HIP : SHK_OK;
+    for (uint32_t j = 0; j < u->W && !rc; j++) if (dmalloc(&G.mk[j], nm)) rc = SHK_ERR_HIP;
+    if (!rc && hipMemsetAsync(G.mv, 0, nm * 4, c->stream) != hipSuccess) rc = SHK_ERR_HIP;
+    if (!rc) {
+      G.mmask = (uint32_t)(nm - 1); u->mcap = (uint32_t)nm;
+      if (ocap) {
+        SHK_BY_WORDS(u->W, hipLaunchKernelGGL(k_ug_rehash<KW>, dim3((ocap + 255) / 256), dim3(256), 0, c->stream, G, old, ocap));
+        if (hipStreamSynchronize(c->stream) != hipSuccess) rc = SHK_ERR_HIP;
+      }
     }
+    for (int j = 0; j < SHK_KM_WMAX; j++) hipFree(old.mk[j]);
+    hipFree(old.mv);
+    if (rc) return rc;
   }
   if (!u->ccap) {
     const uint64_t ncs = 1 << 16;
@@ -2492,21 +2515,18 @@ static int ug_bind(shk_unitig_set *u, shk_ctx *c, uint32_t k, uint64_t amin, uin
     hipFree(d_scal); hipFree(d_stats); if (h_scal) hipHostFree(h_scal);
     return SHK_ERR_HIP;
   }
-  u->c = c; u->k = k; u->amin = amin; u->max_len = max_len;
+  u->c = c; u->k = k; u->amin = amin; u->max_len = max_len; u->W = shk_walk_words(k);
   u->d_scal = d_scal; u->d_stats = d_stats; u->h_scal = h_scal;
   u->G.ncontigs = u->d_scal; u->G.next_n = u->d_scal + 1; u->G.flags = u->d_scal + 2; u->G.stats = u->d_stats;
   int rc = ug_reserve(u, 1024, 1024);
   if (rc) {           // release what the half-made set holds and unbind it
     hipStreamSynchronize(c->stream);
-    ShkUG &G = u->G;
-    hipFree(G.first_lo); hipFree(G.first_hi); hipFree(G.cur_lo); hipFree(G.cur_hi); hipFree(G.rc_lo); hipFree(G.rc_hi);
-    hipFree(G.fh); hipFree(G.rh); hipFree(G.hmin); hipFree(G.len); hipFree(G.l1); hipFree(G.cnt0); hipFree(G.state); hipFree(G.kind);
-    hipFree(G.stop); hipFree(G.mk_lo); hipFree(G.mk_hi); hipFree(G.mv); hipFree(G.ck); hipFree(G.cv);
+    ug_free_arrays(u->G);
     hipFree(u->d_list[0]); hipFree(u->d_list[1]); hipFree(u->d_scal); hipFree(u->d_stats); hipHostFree(u->h_scal);
     memset(&u->G, 0, sizeof(u->G));
     u->d_list[0] = u->d_list[1] = nullptr; u->d_scal = nullptr; u->d_stats = nullptr; u->h_scal = nullptr;
     u->cap = u->mcap = u->ccap = u->lcap = 0;
-    u->c = nullptr;
+    u->c = nullptr; u->W = 0;
   }
   return rc;
 }
@@ -2531,8 +2551,9 @@ static int ug_run(shk_unitig_set *u, uint32_t nactive, int mark) {
     HIPCHK(hipMemcpyAsync(u->d_scal, u->h_scal, 12, hipMemcpyHostToDevice, c->stream));
     u->G.next = u->d_list[cur ^ 1];
     { ProfScope ps(c, KP_UG_WALK);
-      hipLaunchKernelGGL(k_ug_walk, dim3((nactive + 7) / 8), dim3(64), 0, c->stream, u->G, (const uint32_t *)u->d_list[cur], nactive, c->tab[c->cur], c->q_lo,
-                         c->nslots, c->cfg.hb, u->k, u->amin, mark ? 1 : 2, step, u->max_len); }
+      SHK_BY_WORDS(u->W,
+        hipLaunchKernelGGL(k_ug_walk<KW>, dim3((nactive + 7) / 8), dim3(64), 0, c->stream, u->G, (const uint32_t *)u->d_list[cur], nactive, c->tab[c->cur],
+                           c->q_lo, c->nslots, c->cfg.hb, u->k, u->amin, mark ? 1 : 2, step, u->max_len)); }
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(u->h_scal, u->d_scal, 12, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -2562,8 +2583,9 @@ extern "C" int shk_unitigs_add_seeds(shk_ctx *c, shk_unitig_set *u, const char *
   if (rc) return rc;
   HIPCHK(hipMemcpyAsync(u->d_seeds, seeds, (size_t)n * k, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(u->d_counts, seed_counts, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-  hipLaunchKernelGGL(k_ug_add_seeds, dim3((n + 255) / 256), dim3(256), 0, c->stream, u->G, (const char *)u->d_seeds, (const uint32_t *)u->d_counts, n, k,
-                     u->ncontigs, u->d_list[0]);
+  SHK_BY_WORDS(u->W,
+    hipLaunchKernelGGL(k_ug_add_seeds<KW>, dim3((n + 255) / 256), dim3(256), 0, c->stream, u->G, (const char *)u->d_seeds, (const uint32_t *)u->d_counts, n, k,
+                       u->ncontigs, u->d_list[0]));
   HIPCHK(hipGetLastError());
   u->ncontigs += n;
   rc = ug_run(u, n, mark_traveled);
@@ -2609,8 +2631,9 @@ extern "C" int shk_unitigs_add_reads(shk_ctx *c, shk_unitig_set *u, const void *
                          c->cfg.hb, dtext, c->d_rd_start, c->d_rd_end, lo, hi, k, count_min, count_max, 1, u->d_seeds, u->d_counts); }
     u->h_scal[0] = u->ncontigs; u->h_scal[1] = 0; u->h_scal[2] = 0; u->h_scal[3] = 0;
     HIPCHK(hipMemcpyAsync(u->d_scal, u->h_scal, 16, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_ug_seeds_from_reads, dim3((uint32_t)((m + 255) / 256)), dim3(256), 0, c->stream, u->G, (const char *)u->d_seeds,
-                       (const uint32_t *)u->d_counts, lo, hi, k, u->d_list[0], u->d_scal + 3);
+    SHK_BY_WORDS(u->W,
+      hipLaunchKernelGGL(k_ug_seeds_from_reads<KW>, dim3((uint32_t)((m + 255) / 256)), dim3(256), 0, c->stream, u->G, (const char *)u->d_seeds,
+                         (const uint32_t *)u->d_counts, lo, hi, k, u->d_list[0], u->d_scal + 3));
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(u->h_scal, u->d_scal, 16, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -2644,7 +2667,7 @@ extern "C" int shk_unitig_set_write(shk_unitig_set *u, uint32_t k, const char *o
   uint64_t *d_newid = nullptr, *d_off = nullptr, *d_uoff = nullptr, *d_sums = nullptr;
   char *d_bases = nullptr;
   int32_t *d_med = nullptr, *d_links = nullptr;
-  uint64_t *m_lo = nullptr, *m_hi = nullptr; uint32_t *m_v = nullptr;
+  uint64_t *m_k[SHK_KM_WMAX] = {}; uint32_t *m_v = nullptr;
   int rc = SHK_OK;
   std::vector<char> bases;
   std::vector<uint64_t> uoff;
@@ -2657,7 +2680,7 @@ extern "C" int shk_unitig_set_write(shk_unitig_set *u, uint32_t k, const char *o
     // after all the walks)
     if (dmalloc(&d_sums, (uint64_t)n / SHK_SCAN_TILE + 8)) { rc = SHK_ERR_HIP; break; }
     if (dmalloc(&d_keep, (uint64_t)n + 1) || dmalloc(&d_lens, (uint64_t)n + 1) || dmalloc(&d_newid, (uint64_t)n + 2) || dmalloc(&d_off, (uint64_t)n + 2)) { rc = SHK_ERR_HIP; break; }
-    hipLaunchKernelGGL(k_ug_check, dim3((n + 255) / 256), dim3(256), 0, c->stream, u->G, n, d_keep, d_lens);
+    SHK_BY_WORDS(u->W, hipLaunchKernelGGL(k_ug_check<KW>, dim3((n + 255) / 256), dim3(256), 0, c->stream, u->G, n, d_keep, d_lens));
     if (getenv("SHK_UG_DEBUG")) {   // diagnostics: contigs by kind, state and last stop reason
       std::vector<uint8_t> hs(n), hk(n), hp(n);
       std::vector<uint32_t> hkeep(n);
@@ -2683,19 +2706,24 @@ extern "C" int shk_unitig_set_write(shk_unitig_set *u, uint32_t k, const char *o
     if (dmalloc(&d_bases, total + 16) || dmalloc(&d_cnt, total + 16) || dmalloc(&d_uoff, nunits + 1) || dmalloc(&d_ulen, nunits + 1) ||
         dmalloc(&d_ul1, nunits + 1) || dmalloc(&d_med, nunits + 1) || dmalloc(&d_links, nunits * 8 + 8)) { rc = SHK_ERR_HIP; break; }
     { ProfScope ps(c, KP_UG_FINISH);
-      hipLaunchKernelGGL(k_ug_emit, dim3((n + 63) / 64), dim3(64), 0, c->stream, u->G, n, (const uint32_t *)d_keep, (const uint64_t *)d_newid, (const uint64_t *)d_off,
-                         c->tab[c->cur], c->q_lo, c->nslots, c->cfg.hb, k, u->amin, d_bases, d_cnt, d_uoff, d_ulen, d_ul1); }
+      SHK_BY_WORDS(u->W,
+        hipLaunchKernelGGL(k_ug_emit<KW>, dim3((n + 63) / 64), dim3(64), 0, c->stream, u->G, n, (const uint32_t *)d_keep, (const uint64_t *)d_newid,
+                           (const uint64_t *)d_off, c->tab[c->cur], c->q_lo, c->nslots, c->cfg.hb, k, u->amin, d_bases, d_cnt, d_uoff, d_ulen, d_ul1)); }
     hipLaunchKernelGGL(k_ug_median, dim3((uint32_t)nunits), dim3(SHK_WAVE), 0, c->stream, (uint32_t)nunits, (const uint64_t *)d_uoff, (const uint32_t *)d_ulen,
                        (const uint32_t *)d_ul1, (const uint32_t *)d_cnt, k, d_med);
     // the graph pass's own map: first k-mer -> +number, RC(last k-mer) -> -number
     uint64_t nm = 4096;
     while (nm < nunits * 8) nm *= 2;
-    if (dmalloc(&m_lo, nm) || dmalloc(&m_hi, nm) || dmalloc(&m_v, nm)) { rc = SHK_ERR_HIP; break; }
+    if (dmalloc(&m_v, nm)) { rc = SHK_ERR_HIP; break; }
+    for (uint32_t j = 0; j < u->W && !rc; j++) if (dmalloc(&m_k[j], nm)) rc = SHK_ERR_HIP;
+    if (rc) break;
     if (hipMemsetAsync(m_v, 0, nm * 4, c->stream) != hipSuccess) { rc = SHK_ERR_HIP; break; }
     ShkUG G2 = u->G;
-    G2.mk_lo = m_lo; G2.mk_hi = m_hi; G2.mv = m_v; G2.mmask = (uint32_t)(nm - 1);
-    hipLaunchKernelGGL(k_ug_map2, dim3((n + 255) / 256), dim3(256), 0, c->stream, G2, n, (const uint32_t *)d_keep, (const uint64_t *)d_newid);
-    hipLaunchKernelGGL(k_ug_links, dim3((n + 255) / 256), dim3(256), 0, c->stream, G2, n, (const uint32_t *)d_keep, (const uint64_t *)d_newid, k, d_links);
+    for (int j = 0; j < SHK_KM_WMAX; j++) G2.mk[j] = m_k[j];
+    G2.mv = m_v; G2.mmask = (uint32_t)(nm - 1);
+    SHK_BY_WORDS(u->W,
+      hipLaunchKernelGGL(k_ug_map2<KW>, dim3((n + 255) / 256), dim3(256), 0, c->stream, G2, n, (const uint32_t *)d_keep, (const uint64_t *)d_newid);
+      hipLaunchKernelGGL(k_ug_links<KW>, dim3((n + 255) / 256), dim3(256), 0, c->stream, G2, n, (const uint32_t *)d_keep, (const uint64_t *)d_newid, k, d_links));
     if (hipGetLastError() != hipSuccess) { rc = SHK_ERR_HIP; break; }
     bases.resize(total); uoff.resize(nunits); ulen.resize(nunits); med.resize(nunits); links.resize(nunits * 8);
     if (hipMemcpyAsync(bases.data(), d_bases, total, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
@@ -2708,7 +2736,8 @@ extern "C" int shk_unitig_set_write(shk_unitig_set *u, uint32_t k, const char *o
   } while (0);
   hipStreamSynchronize(c->stream);
   hipFree(d_keep); hipFree(d_lens); hipFree(d_newid); hipFree(d_off); hipFree(d_bases); hipFree(d_cnt); hipFree(d_uoff); hipFree(d_ulen);
-  hipFree(d_ul1); hipFree(d_med); hipFree(d_links); hipFree(m_lo); hipFree(m_hi); hipFree(m_v); hipFree(d_sums);
+  hipFree(d_ul1); hipFree(d_med); hipFree(d_links); hipFree(m_v); hipFree(d_sums);
+  for (int j = 0; j < SHK_KM_WMAX; j++) hipFree(m_k[j]);
   if (rc) { fclose(fo); return finish(c, rc); }
   // the records as the reference writes them (:606-626): ids 0-based in final numbering, successors then predecessors.
   // Formatted in slices by a few host threads (two million records are ~6 M numbers to print), written in order

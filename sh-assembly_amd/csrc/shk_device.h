@@ -278,3 +278,125 @@ __device__ __forceinline__ unsigned shk_dec(const uint8_t *s, bool first_is_rune
   *count = cnt + 1;
   return n + 1;
 }
+
+// ---- Contiger's k-mers: 2 bits per base (A,C,G,T = 0..3) in W 64-bit words, the value of the base-4 number
+// s0 s1 .. s(k-1), so the first base sits in the highest used bits, at bit 2(k-1); word 0 holds the lowest 64 bits.
+// W = 2 holds k <= 64 (the unsigned __int128 of earlier versions, word for word), 4 k <= 128, 6 k <= 192. k stays a runtime
+// value: every loop over the words unrolls on the compile-time W, and what depends on k (the first base's word, the mask,
+// the shift of the reverse complement) is a select per word inside those loops -- no per-thread array is ever indexed at
+// run time, so the windows live in registers.
+#define SHK_KM_WMAX 6
+template <int W> struct ShkKmer { uint64_t w[W]; };
+
+template <int W> __device__ __forceinline__ ShkKmer<W> shk_km_zero() {
+  ShkKmer<W> a;
+#pragma unroll
+  for (int j = 0; j < W; j++) a.w[j] = 0;
+  return a;
+}
+// the 2k low bits set
+template <int W> __device__ __forceinline__ ShkKmer<W> shk_km_mask(uint32_t k) {
+  ShkKmer<W> m;
+#pragma unroll
+  for (int j = 0; j < W; j++) {
+    const int bits = 2 * (int)k - 64 * j;
+    m.w[j] = bits >= 64 ? ~0ULL : bits <= 0 ? 0ULL : ((1ULL << bits) - 1);
+  }
+  return m;
+}
+// (a << 2) | c, not masked (packing from text: the value never exceeds 2k bits)
+template <int W> __device__ __forceinline__ ShkKmer<W> shk_km_push(const ShkKmer<W> &a, unsigned c) {
+  ShkKmer<W> r;
+#pragma unroll
+  for (int j = W - 1; j > 0; j--) r.w[j] = (a.w[j] << 2) | (a.w[j - 1] >> 62);
+  r.w[0] = (a.w[0] << 2) | c;
+  return r;
+}
+// append a base: ((a << 2) | c) & mask
+template <int W> __device__ __forceinline__ ShkKmer<W> shk_km_append(const ShkKmer<W> &a, unsigned c, const ShkKmer<W> &mask) {
+  ShkKmer<W> r = shk_km_push(a, c);
+#pragma unroll
+  for (int j = 0; j < W; j++) r.w[j] &= mask.w[j];
+  return r;
+}
+// the base at 2-bit position p (0 = the last base, k - 1 = the first)
+template <int W> __device__ __forceinline__ unsigned shk_km_base(const ShkKmer<W> &a, uint32_t p) {
+  const uint32_t wi = p >> 5, sh = 2 * (p & 31);
+  unsigned c = 0;
+#pragma unroll
+  for (int j = 0; j < W; j++) c = (uint32_t)j == wi ? (unsigned)(a.w[j] >> sh) & 3u : c;
+  return c;
+}
+// (a >> 2) with base c inserted at position k - 1 (the first base)
+template <int W> __device__ __forceinline__ ShkKmer<W> shk_km_push_top(const ShkKmer<W> &a, unsigned c, uint32_t k) {
+  const uint32_t wi = (k - 1) >> 5, sh = 2 * ((k - 1) & 31);
+  ShkKmer<W> r;
+#pragma unroll
+  for (int j = 0; j < W - 1; j++) r.w[j] = (a.w[j] >> 2) | (a.w[j + 1] << 62);
+  r.w[W - 1] = a.w[W - 1] >> 2;
+#pragma unroll
+  for (int j = 0; j < W; j++) r.w[j] |= (uint32_t)j == wi ? (uint64_t)c << sh : 0ULL;
+  return r;
+}
+// the last base replaced by c
+template <int W> __device__ __forceinline__ ShkKmer<W> shk_km_set_last(ShkKmer<W> a, unsigned c) {
+  a.w[0] = (a.w[0] & ~3ULL) | c;
+  return a;
+}
+template <int W> __device__ __forceinline__ bool shk_km_eq(const ShkKmer<W> &a, const ShkKmer<W> &b) {
+  bool e = true;
+#pragma unroll
+  for (int j = 0; j < W; j++) e = e && a.w[j] == b.w[j];
+  return e;
+}
+// reverse complement: complement, reverse the 2-bit groups of every word and the order of the words (the k-mer then
+// fills the top 2k bits), then shift right by 64 W - 2k
+template <int W> __device__ __forceinline__ ShkKmer<W> shk_km_rc(const ShkKmer<W> &a, uint32_t k) {
+  uint64_t t[W];
+#pragma unroll
+  for (int j = 0; j < W; j++) {
+    uint64_t x = ~a.w[W - 1 - j];
+    x = ((x >> 2) & 0x3333333333333333ULL) | ((x & 0x3333333333333333ULL) << 2);
+    x = ((x >> 4) & 0x0F0F0F0F0F0F0F0FULL) | ((x & 0x0F0F0F0F0F0F0F0FULL) << 4);
+    t[j] = __builtin_bswap64(x);
+  }
+  const uint32_t s = 64 * W - 2 * k, q = s >> 6, b = s & 63;
+  ShkKmer<W> r;
+#pragma unroll
+  for (int j = 0; j < W; j++) {
+    uint64_t lo = 0, hi = 0;
+#pragma unroll
+    for (int qq = 0; qq < W; qq++) {
+      if ((uint32_t)qq == q) {
+        lo = j + qq < W ? t[j + qq] : 0ULL;
+        hi = j + qq + 1 < W ? t[j + qq + 1] : 0ULL;
+      }
+    }
+    r.w[j] = b ? (lo >> b) | (hi << (64 - b)) : lo;
+  }
+  return r;
+}
+// the start-k-mer map's hash; at W = 2 the mix of the two halves that the 128-bit keys always had (same probe order)
+__device__ __forceinline__ uint64_t shk_ug_mix(uint64_t lo, uint64_t hi) {
+  uint64_t h = lo * 0x9E3779B97F4A7C15ULL ^ (hi + 0x7F4A7C159E3779B9ULL) * 0xC2B2AE3D27D4EB4FULL;
+  h ^= h >> 29; h *= 0xBF58476D1CE4E5B9ULL; h ^= h >> 32;
+  return h;
+}
+template <int W> __device__ __forceinline__ uint64_t shk_km_mix(const ShkKmer<W> &a) {
+  static_assert(W % 2 == 0, "pairs of words");
+  uint64_t h = shk_ug_mix(a.w[0], a.w[1]);
+#pragma unroll
+  for (int j = 2; j < W; j += 2) h = shk_ug_mix(h ^ a.w[j], a.w[j + 1]);
+  return h;
+}
+// word planes: plane j holds word j of every entry (neighbouring entries stay coalesced)
+template <int W> __device__ __forceinline__ ShkKmer<W> shk_km_load(uint64_t *const (&p)[SHK_KM_WMAX], size_t i) {
+  ShkKmer<W> a;
+#pragma unroll
+  for (int j = 0; j < W; j++) a.w[j] = p[j][i];
+  return a;
+}
+template <int W> __device__ __forceinline__ void shk_km_store(uint64_t *const (&p)[SHK_KM_WMAX], size_t i, const ShkKmer<W> &a) {
+#pragma unroll
+  for (int j = 0; j < W; j++) p[j][i] = a.w[j];
+}

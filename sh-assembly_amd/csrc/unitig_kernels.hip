@@ -4,7 +4,7 @@
 //
 // Reference (src/contig_assembly.cpp)                       here
 //   contigs (concurrent_vector<Contig>)                     ShkUG contig arrays (first/last k-mer as 2 bits per base in
-//                                                           128 bits, rolling hashes, length, state)
+//                                                           W word planes, rolling hashes, length, state)
 //   startKmer2unitig (tbb::concurrent_hash_map)  :3018-3025 open-addressing table keyed by the packed k-mer, value = contig id,
 //                                                           "smaller id wins" as an atomic minimum (ug_put)
 //   WorkQueue of branch neighbours               :847-882   `next` list filled by the walk kernel, swapped by the host per round
@@ -21,9 +21,11 @@
 // A walk stores nothing but its end state: the bases of the kept unitigs are produced afterwards by walking each once
 // more from its first k-mer into an exactly sized arena (the path is unambiguous: a walk only ever extends through a
 // k-mer with one solid successor that has one solid predecessor). Sequences never travel to the host before the end.
+//
+// Every kernel that holds a k-mer is a template on W, the 64-bit words of a packed k-mer (ShkKmer, shk_device.h): 2, 4
+// or 6 for k <= 64, 128, 191. The set picks W once from its k (shk_walk_words); k-mer arrays and map keys are W planes of
+// words, plane j = word j of every entry.
 #include "shk_device.h"
-
-typedef unsigned __int128 shk_u128;
 
 #define SHK_UG_UNUSED 0
 #define SHK_UG_OPEN 1
@@ -35,14 +37,15 @@ typedef unsigned __int128 shk_u128;
 
 struct ShkUG {
   // contigs (index = contig id, ids start at 1 like the reference's contigs.resize(1))
-  uint64_t *first_lo, *first_hi, *cur_lo, *cur_hi, *rc_lo, *rc_hi, *fh, *rh, *hmin;
+  uint64_t *first[SHK_KM_WMAX], *cur[SHK_KM_WMAX], *rc[SHK_KM_WMAX];   // word planes (W of them are allocated)
+  uint64_t *fh, *rh, *hmin;
   uint32_t *len, *l1, *cnt0;
   uint8_t *state, *kind, *stop;      // kind: bit 0 = seed (walked both ways), bit 1 = second call running, bit 2 = hashes not yet computed,
                                      // bit 3 + bits 4-5 = the base onto RC(seed) (k_ug_emit), bit 6 = a pure circle (the circle set decides who keeps it)
   uint32_t cap;
   uint32_t *ncontigs;                // next free id
   // start-k-mer map
-  uint64_t *mk_lo, *mk_hi;
+  uint64_t *mk[SHK_KM_WMAX];          // key word planes
   uint32_t *mv;
   uint32_t mmask;
   // pure circles: minimum canonical hash over the circle's k-mers -> contig id (the same circle cut elsewhere collides)
@@ -55,56 +58,44 @@ struct ShkUG {
   unsigned long long *stats;         // 0 extensions, 1 duplicates (cleared), 2 truncated, 3 candidates queued
 };
 
-__device__ __forceinline__ uint64_t shk_ug_mix(uint64_t lo, uint64_t hi) {
-  uint64_t h = lo * 0x9E3779B97F4A7C15ULL ^ (hi + 0x7F4A7C159E3779B9ULL) * 0xC2B2AE3D27D4EB4FULL;
-  h ^= h >> 29; h *= 0xBF58476D1CE4E5B9ULL; h ^= h >> 32;
-  return h;
+// the map's key at slot i equals `key` (word 0 first: most slots differ there)
+template <int W> __device__ __forceinline__ bool shk_ug_key_at(const ShkUG &G, uint32_t i, const ShkKmer<W> &key) {
+  bool e = true;
+#pragma unroll
+  for (int j = 0; j < W; j++) e = e && G.mk[j][i] == key.w[j];
+  return e;
 }
-// reverse complement of a k-mer packed 2 bits per base, first base in the highest used bits
-__device__ __forceinline__ shk_u128 shk_ug_rc(shk_u128 w, uint32_t k) {
-  uint64_t lo = ~(uint64_t)w, hi = ~(uint64_t)(w >> 64);
-  // reverse the 2-bit groups of each half, then swap the halves
-#define SHK_REV2(x) do { x = ((x >> 2) & 0x3333333333333333ULL) | ((x & 0x3333333333333333ULL) << 2); \
-                         x = ((x >> 4) & 0x0F0F0F0F0F0F0F0FULL) | ((x & 0x0F0F0F0F0F0F0F0FULL) << 4); \
-                         x = __builtin_bswap64(x); } while (0)
-  SHK_REV2(lo); SHK_REV2(hi);
-#undef SHK_REV2
-  const shk_u128 r = ((shk_u128)lo << 64) | hi;
-  return k == 64 ? r : (r >> (128 - 2 * k));
-}
-__device__ __forceinline__ shk_u128 shk_ug_mask(uint32_t k) { return k == 64 ? ~(shk_u128)0 : (((shk_u128)1 << (2 * k)) - 1); }
 
 // value of `key` in the start-k-mer map, 0 when absent
-__device__ __forceinline__ uint32_t shk_ug_find(const ShkUG &G, shk_u128 key) {
-  const uint64_t lo = (uint64_t)key, hi = (uint64_t)(key >> 64);
-  uint32_t i = (uint32_t)shk_ug_mix(lo, hi) & G.mmask;
+template <int W> __device__ __forceinline__ uint32_t shk_ug_find(const ShkUG &G, const ShkKmer<W> &key) {
+  uint32_t i = (uint32_t)shk_km_mix(key) & G.mmask;
   for (uint32_t probes = 0; probes <= G.mmask; probes++) {
     const uint32_t v = __hip_atomic_load(&G.mv[i], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
     // a slot that is being filled right now counts as the end of the probe sequence: every key inserted BEFORE it was
     // claimed sits at or in front of it, so "absent" is a correct answer for this moment
     if (v == 0 || v == SHK_UG_BUSY) return 0;
-    if (G.mk_lo[i] == lo && G.mk_hi[i] == hi) return v;
+    if (shk_ug_key_at(G, i, key)) return v;
     i = (i + 1) & G.mmask;
   }
   return 0;
 }
 // insert_or_replace (contig_assembly.cpp:3018-3025): the key ends up mapped to min(existing, id); true when that is `id`.
 // only_if_absent: a plain insert that reports whether the key was new (the work queue's test, :3137, :3150).
-__device__ __forceinline__ bool shk_ug_put(const ShkUG &G, shk_u128 key, uint32_t id, bool only_if_absent) {
-  const uint64_t lo = (uint64_t)key, hi = (uint64_t)(key >> 64);
-  uint32_t i = (uint32_t)shk_ug_mix(lo, hi) & G.mmask;
+template <int W> __device__ __forceinline__ bool shk_ug_put(const ShkUG &G, const ShkKmer<W> &key, uint32_t id, bool only_if_absent) {
+  uint32_t i = (uint32_t)shk_km_mix(key) & G.mmask;
   for (uint32_t probes = 0; probes <= G.mmask;) {
     const uint32_t v = __hip_atomic_load(&G.mv[i], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
     if (v == 0) {
       if (atomicCAS(&G.mv[i], 0u, SHK_UG_BUSY) == 0u) {       // claimed: key first, then the value makes it visible
-        G.mk_lo[i] = lo; G.mk_hi[i] = hi;
+#pragma unroll
+        for (int j = 0; j < W; j++) G.mk[j][i] = key.w[j];
         __hip_atomic_store(&G.mv[i], id, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
         return true;
       }
       continue;                                               // somebody else claimed it: look again
     }
     if (v == SHK_UG_BUSY) continue;                           // its owner publishes within its own loop iteration
-    if (G.mk_lo[i] == lo && G.mk_hi[i] == hi) {
+    if (shk_ug_key_at(G, i, key)) {
       if (only_if_absent) return false;
       uint32_t old = v;
       while (old > id) {
@@ -160,22 +151,29 @@ __device__ __forceinline__ uint32_t shk_ug_circle_find(const ShkUG &G, uint64_t 
 }
 
 // canonical ntHash of a packed k-mer from scratch (base/nthash.hpp:295-302)
-__device__ __forceinline__ void shk_ug_hash(shk_u128 w, uint32_t k, uint64_t *fh, uint64_t *rh) {
+// (word by word: base j of the k-mer sits at 2-bit position p = k - 1 - j)
+template <int W> __device__ __forceinline__ void shk_ug_hash(const ShkKmer<W> &w, uint32_t k, uint64_t *fh, uint64_t *rh) {
   uint64_t f = 0, r = 0;
-  for (uint32_t j = 0; j < k; j++) {
-    const unsigned c = (unsigned)(w >> (2 * (k - 1 - j))) & 3u;
-    f ^= shk_rol64(shk_code_seed(c), (k - 1 - j) & 63);
-    r ^= shk_rol64(shk_code_seed_rc(c), j & 63);
+#pragma unroll
+  for (int wi = 0; wi < W; wi++) {
+    const uint32_t p0 = 32u * wi;
+    const uint32_t np = k > p0 ? (k - p0 < 32u ? k - p0 : 32u) : 0u;
+    for (uint32_t b = 0; b < np; b++) {
+      const uint32_t p = p0 + b;
+      const unsigned c = (unsigned)(w.w[wi] >> (2 * b)) & 3u;
+      f ^= shk_rol64(shk_code_seed(c), p & 63);
+      r ^= shk_rol64(shk_code_seed_rc(c), (k - 1 - p) & 63);
+    }
   }
   *fh = f; *rh = r;
 }
 
 // a new contig that consists of one k-mer (Contig(kmer, count), :3139, :3152, :1878)
-__device__ __forceinline__ void shk_ug_init(const ShkUG &G, uint32_t id, shk_u128 kmer, uint32_t k, uint32_t count, uint8_t kind) {
-  const shk_u128 rc = shk_ug_rc(kmer, k);
-  G.first_lo[id] = (uint64_t)kmer; G.first_hi[id] = (uint64_t)(kmer >> 64);
-  G.cur_lo[id] = (uint64_t)kmer; G.cur_hi[id] = (uint64_t)(kmer >> 64);
-  G.rc_lo[id] = (uint64_t)rc; G.rc_hi[id] = (uint64_t)(rc >> 64);
+template <int W>
+__device__ __forceinline__ void shk_ug_init(const ShkUG &G, uint32_t id, const ShkKmer<W> &kmer, uint32_t k, uint32_t count, uint8_t kind) {
+  shk_km_store(G.first, id, kmer);
+  shk_km_store(G.cur, id, kmer);
+  shk_km_store(G.rc, id, shk_km_rc(kmer, k));
   G.fh[id] = 0; G.rh[id] = 0; G.hmin[id] = ~0ULL;
   G.len[id] = k; G.l1[id] = k; G.cnt0[id] = count;
   G.kind[id] = (uint8_t)(kind | 4u);
@@ -185,32 +183,34 @@ __device__ __forceinline__ void shk_ug_init(const ShkUG &G, uint32_t id, shk_u12
 
 // seeds given as text (n * k upper-case bases): contigs first_id .. first_id + n - 1, in order; a seed with a byte that
 // is not a base gives an unused contig
+template <int W>
 __global__ void k_ug_add_seeds(ShkUG G, const char *seeds, const uint32_t *counts, uint32_t n, uint32_t k, uint32_t first_id,
                                uint32_t *active) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const uint32_t id = first_id + i;
-  shk_u128 w = 0;
+  ShkKmer<W> w = shk_km_zero<W>();
   bool bad = false;
   for (uint32_t j = 0; j < k; j++) {
     const char c = seeds[(size_t)i * k + j];
     const unsigned cc = c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : c == 'T' ? 3u : 4u;
     if (cc > 3) bad = true;
-    w = (w << 2) | (cc & 3u);
+    w = shk_km_push(w, cc & 3u);
   }
   active[i] = id;
   if (bad) { G.state[id] = SHK_UG_UNUSED; G.len[id] = 0; return; }
   shk_ug_init(G, id, w, k, counts[i], 1);
 }
 // seeds straight from the reads of a batch (k_select_seeds' per-read output: count 0 = no seed): compacted into new contigs
+template <int W>
 __global__ void k_ug_seeds_from_reads(ShkUG G, const char *seeds, const uint32_t *counts, uint64_t read_lo, uint64_t nreads, uint32_t k,
                                       uint32_t *active, uint32_t *nactive) {
   const uint64_t r = read_lo + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= nreads || counts[r] == 0) return;
-  shk_u128 w = 0;
+  ShkKmer<W> w = shk_km_zero<W>();
   for (uint32_t j = 0; j < k; j++) {
     const char c = seeds[r * k + j];
-    w = (w << 2) | (c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : 3u);
+    w = shk_km_push(w, c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : 3u);
   }
   const uint32_t id = atomicAdd(G.ncontigs, 1u);
   if (id >= G.cap) { atomicOr(G.flags, SHK_UG_E_CONTIGS); return; }
@@ -226,6 +226,7 @@ __global__ void k_ug_seeds_from_reads(ShkUG G, const char *seeds, const uint32_t
 // verdicts meet in a wave ballot; every lane keeps the walk's state and decides alike; lane 0 owns the contig's
 // records, a lane that found a candidate queues it itself.
 #define SHK_UG_LANES 8
+template <int W>
 __global__ void __launch_bounds__(SHK_WAVE) k_ug_walk(ShkUG G, const uint32_t *active, uint32_t nactive, uint8_t *tab, uint64_t q_lo,
                                                       uint64_t nslots, uint32_t hb, uint32_t k, uint64_t amin, int mark, uint32_t max_steps,
                                                       uint32_t max_len) {
@@ -237,15 +238,15 @@ __global__ void __launch_bounds__(SHK_WAVE) k_ug_walk(ShkUG G, const uint32_t *a
   const uint32_t id = alive ? active[grp] : 0;
   if (alive && G.state[id] != SHK_UG_OPEN) alive = false;
   const uint64_t kmask = hb >= 64 ? ~0ULL : ((1ULL << hb) - 1);
-  const shk_u128 wmask = shk_ug_mask(k);
-  shk_u128 win = 0, rcw = 0, first = 0;
+  const ShkKmer<W> wmask = shk_km_mask<W>(k);
+  ShkKmer<W> win = shk_km_zero<W>(), rcw = shk_km_zero<W>(), first = shk_km_zero<W>();
   uint64_t fh = 0, rh = 0, hmin = ~0ULL;
   uint32_t len = 0;
   uint8_t kind = 0;
   if (alive) {
-    win = ((shk_u128)G.cur_hi[id] << 64) | G.cur_lo[id];
-    rcw = ((shk_u128)G.rc_hi[id] << 64) | G.rc_lo[id];
-    first = ((shk_u128)G.first_hi[id] << 64) | G.first_lo[id];
+    win = shk_km_load<W>(G.cur, id);
+    rcw = shk_km_load<W>(G.rc, id);
+    first = shk_km_load<W>(G.first, id);
     fh = G.fh[id]; rh = G.rh[id]; hmin = G.hmin[id];
     len = G.len[id]; kind = G.kind[id];
   }
@@ -264,8 +265,8 @@ __global__ void __launch_bounds__(SHK_WAVE) k_ug_walk(ShkUG G, const uint32_t *a
       }
       if (steps >= max_steps) {                                // goes on in the next launch
         if (sub == 0) {
-          G.cur_lo[id] = (uint64_t)win; G.cur_hi[id] = (uint64_t)(win >> 64);
-          G.rc_lo[id] = (uint64_t)rcw; G.rc_hi[id] = (uint64_t)(rcw >> 64);
+          shk_km_store(G.cur, id, win);
+          shk_km_store(G.rc, id, rcw);
           G.fh[id] = fh; G.rh[id] = rh; G.hmin[id] = hmin; G.len[id] = len; G.kind[id] = kind;
           G.next[atomicAdd(G.next_n, 1u)] = id;
         }
@@ -274,15 +275,15 @@ __global__ void __launch_bounds__(SHK_WAVE) k_ug_walk(ShkUG G, const uint32_t *a
     }
     if (alive) {
       steps++;
-      s0 = (unsigned)(win >> (2 * (k - 1))) & 3u;
+      s0 = shk_km_base(win, k - 1);
       uint64_t f, r;
-      shk_u128 key;
+      ShkKmer<W> key;
       bool mine = true;
       if (sub < 4) {
         // k-mers with current[1..] as prefix (:3064-3087)
         f = shk_rol64(fh, 1) ^ shk_rol64(shk_code_seed(s0), k & 63) ^ shk_code_seed(sub);
         r = shk_ror64(rh ^ shk_code_seed_rc(s0), 1) ^ shk_rol64(shk_code_seed_rc(sub), (k - 1) & 63);
-        key = ((win << 2) | sub) & wmask;
+        key = shk_km_append(win, sub, wmask);
       } else {
         // k-mers with RC(current[1..]) as prefix: the other predecessors of my successors (:3090-3120). In the reverse
         // orientation they are RC(current) with its last base replaced; base y there <=> sibling base 3 - y here
@@ -290,7 +291,7 @@ __global__ void __launch_bounds__(SHK_WAVE) k_ug_walk(ShkUG G, const uint32_t *a
         mine = y != 3u - s0;
         f = fh ^ shk_rol64(shk_code_seed(s0) ^ shk_code_seed(z), (k - 1) & 63);
         r = rh ^ shk_code_seed_rc(s0) ^ shk_code_seed_rc(z);
-        key = (rcw & ~(shk_u128)3) | y;
+        key = shk_km_set_last(rcw, y);
       }
       if (mine) {
         uint8_t trav;
@@ -317,8 +318,7 @@ __global__ void __launch_bounds__(SHK_WAVE) k_ug_walk(ShkUG G, const uint32_t *a
         if (sub == 0) ok = shk_ug_put(G, rcw, id, false);
       } else if (ncand == 1) {
         xc = (unsigned)__ffs((int)(cand_m & 0xFu)) - 1;
-        const shk_u128 nxt = ((win << 2) | xc) & wmask;
-        if (nxt == first) {
+        if (shk_km_eq(shk_km_append(win, xc, wmask), first)) {
           // a pure circle (:3176-3183). The reference registers first k-mer and RC(last k-mer) here, keys that depend on
           // where the seed cut the circle. Seeds of one batch that lie on the same circle all get this far at the same
           // time, each with its own cut; their keys would then stop each other's later steps as "known nodes" and leave
@@ -344,8 +344,8 @@ __global__ void __launch_bounds__(SHK_WAVE) k_ug_walk(ShkUG G, const uint32_t *a
     if (alive && extend) {
       const uint64_t f = shk_rol64(fh, 1) ^ shk_rol64(shk_code_seed(s0), k & 63) ^ shk_code_seed(xc);
       const uint64_t r = shk_ror64(rh ^ shk_code_seed_rc(s0), 1) ^ shk_rol64(shk_code_seed_rc(xc), (k - 1) & 63);
-      win = ((win << 2) | xc) & wmask;
-      rcw = (rcw >> 2) | ((shk_u128)(3u - xc) << (2 * (k - 1)));
+      win = shk_km_append(win, xc, wmask);
+      rcw = shk_km_push_top(rcw, 3u - xc, k);
       fh = f; rh = r;
       const uint64_t hc = fh < rh ? fh : rh;
       if (hc < hmin) hmin = hc;
@@ -355,7 +355,7 @@ __global__ void __launch_bounds__(SHK_WAVE) k_ug_walk(ShkUG G, const uint32_t *a
     if (closing) {
       if (branch && closed_ok && ((cand_m >> sub) & 1u)) {
         // my neighbour is a candidate: it becomes a contig of one k-mer unless somebody has queued it already (:3133-3160)
-        const shk_u128 key = sub < 4 ? (((win << 2) | sub) & wmask) : ((rcw & ~(shk_u128)3) | (sub - 4));
+        const ShkKmer<W> key = sub < 4 ? shk_km_append(win, sub, wmask) : shk_km_set_last(rcw, sub - 4);
         if (!shk_ug_find(G, key)) {                            // (cheap pre-check: most neighbours are known already)
           const uint32_t nid = atomicAdd(G.ncontigs, 1u);
           if (nid >= G.cap) atomicOr(G.flags, SHK_UG_E_CONTIGS);
@@ -381,20 +381,20 @@ __global__ void __launch_bounds__(SHK_WAVE) k_ug_walk(ShkUG G, const uint32_t *a
       else if (v != id) turn = true;
     }
     if (sub == 0) {
-      G.cur_lo[id] = (uint64_t)win; G.cur_hi[id] = (uint64_t)(win >> 64);
-      G.rc_lo[id] = (uint64_t)rcw; G.rc_hi[id] = (uint64_t)(rcw >> 64);
+      shk_km_store(G.cur, id, win);
+      shk_km_store(G.rc, id, rcw);
       G.fh[id] = fh; G.rh[id] = rh; G.hmin[id] = hmin; G.len[id] = len;
       G.stop[id] = (uint8_t)((G.stop[id] << 4) | stop);
       if (nstate == SHK_UG_CLEARED) atomicAdd(&G.stats[1], 1ULL);
     }
     if (turn) {
-      const shk_u128 nfirst = rcw, ncur = shk_ug_rc(first, k), nrc = first;
+      const ShkKmer<W> nfirst = rcw, ncur = shk_km_rc(first, k), nrc = first;
       first = nfirst; win = ncur; rcw = nrc;
       // the seed k-mer itself need not be solid for extensions (its count is tested against -x/-X, the walk's
       // neighbours against -s): k_ug_emit, which follows solid successors, is told the one base it cannot find that way --
       // the last base of RC(seed), appended at position l1 - 1 of the final orientation (bit 3 + bits 4-5 of kind)
-      kind = (uint8_t)((kind & 0x07u) | 2u | 4u | 8u | ((3u - ((unsigned)(nrc >> (2 * (k - 1))) & 3u)) << 4));
-      if (sub == 0) { G.first_lo[id] = (uint64_t)first; G.first_hi[id] = (uint64_t)(first >> 64); G.l1[id] = len; }
+      kind = (uint8_t)((kind & 0x07u) | 2u | 4u | 8u | ((3u - shk_km_base(nrc, k - 1)) << 4));
+      if (sub == 0) { shk_km_store(G.first, id, first); G.l1[id] = len; }
       continue;                                                // second call, same lanes, remaining step budget
     }
     if (nstate == SHK_UG_CLOSED && stop == SHK_STOP_CIRCLE) kind |= 0x40u;      // owned through the circle set (k_ug_check)
@@ -407,13 +407,14 @@ __global__ void __launch_bounds__(SHK_WAVE) k_ug_walk(ShkUG G, const uint32_t *a
 // after all walks: a contig survives when both of its keys still map to it (check_unitig :935-954 tests the first k-mer; the
 // walk itself gives up a contig whose end belongs to a smaller one, :3132, :3196, :3204 -- here both tests are final) and,
 // for a pure circle, when it owns the circle. keep[id] = 1 / 0.
+template <int W>
 __global__ void k_ug_check(ShkUG G, uint32_t n, uint32_t *keep, uint32_t *lens) {
   const uint32_t id = blockIdx.x * blockDim.x + threadIdx.x;
   if (id >= n) return;
   uint32_t kp = 0;
   if (id >= 1 && G.state[id] == SHK_UG_CLOSED) {
-    const shk_u128 first = ((shk_u128)G.first_hi[id] << 64) | G.first_lo[id];
-    const shk_u128 rcw = ((shk_u128)G.rc_hi[id] << 64) | G.rc_lo[id];
+    const ShkKmer<W> first = shk_km_load<W>(G.first, id);
+    const ShkKmer<W> rcw = shk_km_load<W>(G.rc, id);
     if (G.kind[id] & 0x40u) kp = shk_ug_circle_find(G, G.hmin[id]) == id;               // a pure circle: the circle set's owner
     else kp = shk_ug_find(G, first) == id && shk_ug_find(G, rcw) == id;
     if (!kp) { G.state[id] = SHK_UG_CLEARED; atomicAdd(&G.stats[1], 1ULL); }
@@ -423,20 +424,26 @@ __global__ void k_ug_check(ShkUG G, uint32_t n, uint32_t *keep, uint32_t *lens) 
 }
 
 // the kept contigs once more from their first k-mer: bases (text) and the filter count of every k-mer, into the arena
+template <int W>
 __global__ void k_ug_emit(ShkUG G, uint32_t n, const uint32_t *keep, const uint64_t *newid, const uint64_t *off, uint8_t *tab,
                           uint64_t q_lo, uint64_t nslots, uint32_t hb, uint32_t k, uint64_t amin, char *bases, uint32_t *counts,
                           uint64_t *out_off, uint32_t *out_len, uint32_t *out_l1) {
   const uint32_t id = blockIdx.x * blockDim.x + threadIdx.x;
   if (id >= n || !keep[id]) return;
   const uint64_t kmask = hb >= 64 ? ~0ULL : ((1ULL << hb) - 1);
-  const shk_u128 wmask = shk_ug_mask(k);
-  shk_u128 win = ((shk_u128)G.first_hi[id] << 64) | G.first_lo[id];
+  const ShkKmer<W> wmask = shk_km_mask<W>(k);
+  ShkKmer<W> win = shk_km_load<W>(G.first, id);
   const uint32_t len = G.len[id], l1 = G.l1[id];
   const uint8_t kind = G.kind[id];
   const uint64_t o = off[id];
   const uint64_t u = newid[id];                  // 0-based final number
   out_off[u] = o; out_len[u] = len; out_l1[u] = l1;
-  for (uint32_t j = 0; j < k; j++) bases[o + j] = "ACGT"[(unsigned)(win >> (2 * (k - 1 - j))) & 3u];
+#pragma unroll
+  for (int wi = 0; wi < W; wi++) {                 // the base at 2-bit position p goes to o + k - 1 - p
+    const uint32_t p0 = 32u * wi;
+    const uint32_t np = k > p0 ? (k - p0 < 32u ? k - p0 : 32u) : 0u;
+    for (uint32_t b = 0; b < np; b++) bases[o + k - 1 - (p0 + b)] = "ACGT"[(unsigned)(win.w[wi] >> (2 * b)) & 3u];
+  }
   uint64_t fh, rh;
   shk_ug_hash(win, k, &fh, &rh);
   uint8_t trav;
@@ -445,7 +452,7 @@ __global__ void k_ug_emit(ShkUG G, uint32_t n, const uint32_t *keep, const uint6
     counts[o] = c0 > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)c0;
   }
   for (uint32_t p = k; p < len; p++) {
-    const unsigned s0 = (unsigned)(win >> (2 * (k - 1))) & 3u;
+    const unsigned s0 = shk_km_base(win, k - 1);
     const uint64_t fbase = shk_rol64(fh, 1) ^ shk_rol64(shk_code_seed(s0), k & 63);
     const uint64_t rbase = shk_ror64(rh ^ shk_code_seed_rc(s0), 1);
     unsigned xc = 0;
@@ -466,7 +473,7 @@ __global__ void k_ug_emit(ShkUG G, uint32_t n, const uint32_t *keep, const uint6
     }
     bases[o + p] = "ACGT"[xc];
     counts[o + p - k + 1] = cx > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)cx;
-    win = ((win << 2) | xc) & wmask;
+    win = shk_km_append(win, xc, wmask);
     fh = fx; rh = rx;
   }
 }
@@ -542,41 +549,45 @@ __global__ void __launch_bounds__(SHK_WAVE) k_ug_median(uint32_t nunits, const u
 
 // the graph pass's map (track_kmer_worker :956-1010): first k-mer -> +number, RC(last k-mer) -> -number (numbers from 1),
 // one key only for a unitig whose two keys coincide. Built into a fresh table (G.m*), value = number << 1 | minus.
+template <int W>
 __global__ void k_ug_map2(ShkUG G, uint32_t n, const uint32_t *keep, const uint64_t *newid) {
   const uint32_t id = blockIdx.x * blockDim.x + threadIdx.x;
   if (id >= n || !keep[id]) return;
   const uint32_t num = (uint32_t)newid[id] + 1;
-  const shk_u128 f = ((shk_u128)G.first_hi[id] << 64) | G.first_lo[id], e = ((shk_u128)G.rc_hi[id] << 64) | G.rc_lo[id];
+  const ShkKmer<W> f = shk_km_load<W>(G.first, id), e = shk_km_load<W>(G.rc, id);
   shk_ug_put(G, f, num << 1, false);
-  if (f != e) shk_ug_put(G, e, (num << 1) | 1u, false);
+  if (!shk_km_eq(f, e)) shk_ug_put(G, e, (num << 1) | 1u, false);
 }
 // build_graph_worker (:1012-1084): successors of my last k-1 bases in A,C,G,T order, then of RC(my first k-1 bases) in
 // T,G,C,A order; links[u*8 + i] = signed number (0 = none)
+template <int W>
 __global__ void k_ug_links(ShkUG G, uint32_t n, const uint32_t *keep, const uint64_t *newid, uint32_t k, int32_t *links) {
   const uint32_t id = blockIdx.x * blockDim.x + threadIdx.x;
   if (id >= n || !keep[id]) return;
-  const shk_u128 wmask = shk_ug_mask(k);
-  const shk_u128 first = ((shk_u128)G.first_hi[id] << 64) | G.first_lo[id], last = ((shk_u128)G.cur_hi[id] << 64) | G.cur_lo[id];
+  const ShkKmer<W> wmask = shk_km_mask<W>(k);
+  const ShkKmer<W> first = shk_km_load<W>(G.first, id), last = shk_km_load<W>(G.cur, id);
   int32_t *out = links + (size_t)newid[id] * 8;
   for (unsigned x = 0; x < 4; x++) {
-    const uint32_t v = shk_ug_find(G, ((last << 2) | x) & wmask);
+    const uint32_t v = shk_ug_find(G, shk_km_append(last, x, wmask));
     out[x] = v ? ((v & 1u) ? -(int32_t)(v >> 1) : (int32_t)(v >> 1)) : 0;
   }
   // RC(first k-1 bases) + x = RC(first k-mer) without ITS first base, + x
-  const shk_u128 rcf = shk_ug_rc(first, k);
+  const ShkKmer<W> rcf = shk_km_rc(first, k);
   for (unsigned i = 0; i < 4; i++) {
     const unsigned x = 3u - i;
-    const uint32_t v = shk_ug_find(G, ((rcf << 2) | x) & wmask);
+    const uint32_t v = shk_ug_find(G, shk_km_append(rcf, x, wmask));
     out[4 + i] = v ? ((v & 1u) ? -(int32_t)(v >> 1) : (int32_t)(v >> 1)) : 0;
   }
 }
 
-__global__ void k_ug_rehash(ShkUG G, const uint64_t *ok_lo, const uint64_t *ok_hi, const uint32_t *ov, uint32_t ocap) {
+// the keys and values of the old map (`old`'s mk / mv, ocap slots) into G's
+template <int W>
+__global__ void k_ug_rehash(ShkUG G, ShkUG old, uint32_t ocap) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= ocap) return;
-  const uint32_t v = ov[i];
+  const uint32_t v = old.mv[i];
   if (v == 0 || v == SHK_UG_BUSY) return;
-  shk_ug_put(G, ((shk_u128)ok_hi[i] << 64) | ok_lo[i], v, false);
+  shk_ug_put(G, shk_km_load<W>(old.mk, i), v, false);
 }
 __global__ void k_ug_rehash_circles(ShkUG G, const uint64_t *ok, const uint32_t *ov, uint32_t ocap) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;

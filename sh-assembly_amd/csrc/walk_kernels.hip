@@ -6,7 +6,8 @@
 // between concurrent walks, duplicate removal and the graph passes stay with the host (next rounds).
 //
 // One thread per open end. The k-mer window lives in registers as 2 bits per base (A,C,G,T = 0..3,
-// the order of DNA_bases, base/global.h:110), k <= 64. Per step:
+// the order of DNA_bases, base/global.h:110) in W 64-bit words (ShkKmer, shk_device.h): the kernel is instantiated for
+// W = 2, 4, 6 (k <= 64, 128, 191) and the host picks the smallest that holds k (shk_walk_words). Per step:
 //   after:  the 4 k-mers window[1..] + x                      (contig_assembly.cpp:3067-3088)
 //   before: the 3 siblings z + window[1..], z != window[0]    (:3090-3120: "kmers with RC(current_kmer_fix)
 //           as prefix", minus the current k-mer itself)
@@ -15,13 +16,16 @@
 // Hashes are rolled: for s = s0 s1..s(k-1), fh = XOR rol(seed(si), k-1-i), rh = XOR rol(seedc(si), i):
 //   successor  fh' = rol1(fh) ^ rol(seed(s0), k) ^ seed(x);   rh' = ror1(rh ^ seedc(s0)) ^ rol(seedc(x), k-1)
 //   sibling    fh" = fh ^ rol(seed(s0) ^ seed(z), k-1);       rh" = rh ^ seedc(s0) ^ seedc(z)
-#define SHK_WALK_MAX_K 64   // stop reasons: SHK_STOP_* of include/shk.h
+#define SHK_WALK_MAX_K SHK_MAX_K   // the same k as counting; stop reasons: SHK_STOP_* of include/shk.h
+// words of a k-mer window: the instantiations of the Contiger kernels
+static inline uint32_t shk_walk_words(uint32_t k) { return k <= 64 ? 2 : k <= 128 ? 4 : 6; }
 
 __device__ __forceinline__ uint64_t shk_code_seed(unsigned c) {      // seedTab column 0 by 2-bit code
   return c == 0 ? SHK_SEED_A : c == 1 ? SHK_SEED_C : c == 2 ? SHK_SEED_G : SHK_SEED_T;
 }
 __device__ __forceinline__ uint64_t shk_code_seed_rc(unsigned c) { return shk_code_seed(3 - c); }
 
+template <int W>
 __global__ void k_extend_forward(uint8_t *tab, uint64_t q_lo, uint64_t nslots, uint32_t hb, const char *cur_kmers,
                                  const char *first_kmers, uint32_t n, uint32_t k, uint64_t abundance_min, int mark,
                                  uint32_t max_ext, char *out_bases, uint32_t *out_counts, uint32_t *out_n,
@@ -30,7 +34,7 @@ __global__ void k_extend_forward(uint8_t *tab, uint64_t q_lo, uint64_t nslots, u
   if (i >= n) return;
   const uint64_t kmask = hb >= 64 ? ~0ULL : ((1ULL << hb) - 1);
   // pack the window and the first k-mer; hash the window once
-  unsigned __int128 win = 0, first = 0;
+  ShkKmer<W> win = shk_km_zero<W>(), first = shk_km_zero<W>();
   uint64_t fh = 0, rh = 0;
   bool bad = false;
   for (uint32_t j = 0; j < k; j++) {
@@ -38,18 +42,18 @@ __global__ void k_extend_forward(uint8_t *tab, uint64_t q_lo, uint64_t nslots, u
     const unsigned cc = c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : c == 'T' ? 3u : 4u;
     const unsigned fc = f == 'A' ? 0u : f == 'C' ? 1u : f == 'G' ? 2u : f == 'T' ? 3u : 4u;
     if (cc > 3 || fc > 3) { bad = true; break; }
-    win = (win << 2) | cc;
-    first = (first << 2) | fc;
+    win = shk_km_push(win, cc);
+    first = shk_km_push(first, fc);
     fh ^= shk_rol64(shk_code_seed(cc), (k - 1 - j) & 63);
     rh ^= shk_rol64(shk_code_seed_rc(cc), j & 63);
   }
   if (bad) { out_n[i] = 0; out_stop[i] = SHK_STOP_BAD_SEED; out_branch[i] = 0; return; }
   uint32_t ncount[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // filter counts of the neighbours named in `branch`
-  const unsigned __int128 wmask = k == 64 ? ~(unsigned __int128)0 : (((unsigned __int128)1 << (2 * k)) - 1);
+  const ShkKmer<W> wmask = shk_km_mask<W>(k);
   uint32_t nout = 0;
   uint8_t stop = 0, trav, branch = 0;   // branch: solid successors (bits 0-3, by base) and solid siblings (bits 4-7) at the stop
   while (!stop) {
-    const unsigned s0 = (unsigned)(win >> (2 * (k - 1))) & 3u;
+    const unsigned s0 = shk_km_base(win, k - 1);
     // successors
     const uint64_t fbase = shk_rol64(fh, 1) ^ shk_rol64(shk_code_seed(s0), k & 63);
     const uint64_t rbase = shk_ror64(rh ^ shk_code_seed_rc(s0), 1);
@@ -78,8 +82,8 @@ __global__ void k_extend_forward(uint8_t *tab, uint64_t q_lo, uint64_t nslots, u
       break;
     }
     if (ncand == 0) { stop = SHK_STOP_DEAD_END; break; }
-    const unsigned __int128 next = ((win << 2) | xc) & wmask;
-    if (next == first) { stop = SHK_STOP_CIRCLE; break; }
+    const ShkKmer<W> next = shk_km_append(win, xc, wmask);
+    if (shk_km_eq(next, first)) { stop = SHK_STOP_CIRCLE; break; }
     if (nout >= max_ext) { stop = SHK_STOP_BUFFER; break; }
     out_bases[(size_t)i * max_ext + nout] = "ACGT"[xc];
     out_counts[(size_t)i * max_ext + nout] = cnt_x > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)cnt_x;

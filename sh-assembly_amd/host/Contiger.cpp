@@ -20,10 +20,12 @@
 using namespace std;
 using namespace shk;
 
+static const int kMaxK = 191;   // the library's limit for counting and for the walk (SHK_MAX_K, csrc/kmer_kernels.hip)
+
 static void usage(const char *argv0) {
   cerr << endl << argv0 << "  <options>\nOptions:\n"
        << "  -h [ --help ]                          print help messages\n"
-       << "  -k arg                                 k-mer size\n"
+       << "  -k arg                                 k-mer size (2..191)\n"
        << "  -i [ --input ] arg                     a file containing a list of read file name(s)\n"
        << "  -f [ --format ] arg (=f)               format of the input: g(gzip); b(bzip2); f(plain fastq)\n"
        << "  -c [ --cqf ] arg                       the counting quotient filter built with the same 'k'\n"
@@ -68,6 +70,7 @@ int main(int argc, char *argv[]) {
     else { cerr << "unrecognised option " << a << endl; usage(argv[0]); return 0; }
   }
   if (K < 0 || flist.empty() || cqf.empty()) { usage(argv[0]); return 0; }
+  if (K < 2 || K > kMaxK) { cerr << "Contiger: -k " << K << " is out of range: k must lie in 2.." << kMaxK << endl; return 1; }
 
   // list of read files, opened AS WRITTEN (relative names are relative to the working directory): the reference's
   // Contiger hands the lines to seqFile_batch unchanged (src/contig_assembly.cpp:248-258; its help text asks for

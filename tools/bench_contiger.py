@@ -19,7 +19,7 @@ def build(args):
     import bench
     import shk
     dev = torch.device("cuda:0")
-    L, K = 150, args.k
+    L, K = getattr(args, "read_len", 150), args.k
     genome = torch.randint(0, 4, (args.genome,), dtype=torch.uint8, device=dev, generator=torch.Generator(device=dev).manual_seed(7))
     text = bench.gen_batch_torch(torch, genome, args.reads, L, args.err, 0, 1, dev)
     rec = int(text.numel()) // args.reads
@@ -60,6 +60,7 @@ def main():
     ap.add_argument("--reads", type=int, default=8_000_000)
     ap.add_argument("--err", type=float, default=0.00234)
     ap.add_argument("--k", type=int, default=47)
+    ap.add_argument("--read-len", type=int, default=150)
     ap.add_argument("--qb", type=int, default=29)
     ap.add_argument("--amin", type=int, default=4, help="-s: minimum count of a k-mer used to extend (4 suits 60x; the default 2 of the command line suits ~10x)")
     ap.add_argument("--xmin", type=int, default=4, help="-x: minimum count of a seed")
