@@ -117,7 +117,10 @@ int shk_count_chunks(shk_ctx *ctx, const void *text, int text_on_device, uint64_
  * (cqf/CQF_mt.h:821-931 interleaves reading, hashing and inserting across threads). shk_prepare_chunks starts the front
  * end of a batch and returns at once; shk_count_prepared takes the OLDEST prepared batch through the rebuild (deNoise
  * rounds fire inside it exactly as in shk_count_chunks) and returns its statistics. At most two batches may be prepared
- * ahead (SHK_ERR_BATCH beyond). `text` (host or device) must stay valid until the batch has been counted. A failure of
+ * ahead (SHK_ERR_BATCH beyond). `text` (host or device) must stay valid until the batch has been counted. Device text
+ * must be COMPLETE when shk_prepare_chunks is called: the front end runs on a non-blocking stream of its own, which is
+ * ordered behind the copy of shk_upload_text that filled `text` and behind nothing else -- not behind work queued on the
+ * null stream or any other (synchronise that first). A failure of
  * the front end is returned by the shk_count_prepared of that batch; the table is untouched then. Results are those of
  * shk_count_chunks on the same batches in the same order. Not for sharded contexts (their words go through
  * shk_hash_chunks and the exchange). */
@@ -187,10 +190,10 @@ int shk_stage_words(shk_ctx *ctx, const uint64_t *d_words, uint64_t nwords);
 /* The same from TWO device buffers (a shard's own words, where shk_hash_route_chunks left them, and the words it received):
  * no copy that brings them together first. Neither may lie in the buffer shk_hash_chunks returns (the first partition
  * level writes there): SHK_ERR_ARG. */
+int shk_stage_words_pair(shk_ctx *ctx, const uint64_t *d_words_a, uint64_t nwords_a, const uint64_t *d_words_b, uint64_t nwords_b);
 /* Allocates the two send buffers of shk_route_words / shk_hash_route_chunks now instead of inside their first two calls,
  * and the records of a deNoise point (for callers that keep set-up and steady state apart). Idempotent. */
 int shk_route_reserve(shk_ctx *ctx);
-int shk_stage_words_pair(shk_ctx *ctx, const uint64_t *d_words_a, uint64_t nwords_a, const uint64_t *d_words_b, uint64_t nwords_b);
 int shk_stage_summary(shk_ctx *ctx, uint32_t chunk_lo, uint32_t chunk_hi, int want_chunks, shk_summary *out);
 int shk_stage_commit(shk_ctx *ctx, uint32_t chunk_lo, uint32_t chunk_hi, const shk_summary *s);
 /* try/accept form (what sh-assembly_amd/shk/dist.py uses): shk_stage_try computes everything about

@@ -37,10 +37,46 @@ static const char *kp_names[KP_N] = {
 
 struct PendingEvent { int id; hipEvent_t a, b; };
 
-struct shk_ctx {
+// What a front end (parse, hash or roll, partition) works in: its stream, every buffer it writes, the state of its
+// partition and the kernel times recorded on its stream. A context is one (the serial front end and everything behind
+// it run there); the overlapped front end owns a second (ShkFront). The stage functions take the context for geometry and
+// configuration, which they only read, and one of these for everything they change.
+struct ShkStageBufs {
+  hipStream_t stream = hipStream_t();
+  bool lent = false;            // d_words[] and d_base[nlevels] are lent by the owner batch by batch (bufs_alloc, bufs_free)
+  uint8_t *d_text = nullptr;
+  uint64_t *d_chunk_off = nullptr, *d_chunk_len = nullptr, *d_nlines = nullptr, *d_reads_base = nullptr;
+  uint64_t *d_rd_start = nullptr, *d_rd_end = nullptr;
+  uint16_t *d_rd_chunk = nullptr;         // chunk (within the call) of every read
+  uint32_t *d_nkeys = nullptr;
+  uint64_t *d_key_base = nullptr;
+  uint64_t *d_words[2] = {};
+  uint64_t *d_scalars = nullptr;          // [0] nreads, [1] nwords, [2] scan total scratch, [3] marks
+  uint64_t *d_block_sums = nullptr;
+  uint64_t *d_hist[4] = {};               // per level: nbuckets*P (first level: times its window groups)
+  uint64_t *d_base_sub = nullptr;         // first level with window groups: scanned bases of the (digit, group) sub-buckets
+  uint64_t *d_base[5] = {};               // base[l]: bucket bases entering level l (base[nlevels] = region_base)
+  uint64_t *d_cursor = nullptr;
+  uint32_t *d_tfb = nullptr;
+  uint32_t *d_err = nullptr;
+  uint64_t *h_pinned = nullptr;           // pinned mirror: counters [0, SHK_NCOUNTERS), err [40], scalars [41, 64)
+  uint32_t last_err_bits = 0;
+  uint32_t region_cap = 0;      // how the partitioned words lie: 0 = d_base[nlevels] holds exact offsets; else region r owns the slot
+                                // [r * region_cap, ...) and d_base[nlevels][r] is its END (ShkRpLevel::slot_cap)
+  uint32_t slot_overflows = 0;  // consecutive batches whose slotted last level overflowed; at 2 the slots are switched off
+  int slots_off = 0;
+  const uint64_t *stage2_b = nullptr;     // shk_stage_words_pair: the second source of the first partition level (null = one source)
+  uint64_t stage2_na = 0, stage2_nb = 0;
+  // profiling
+  double prof_ms[KP_N] = {};
+  uint64_t prof_n[KP_N] = {};
+  std::vector<PendingEvent> pending;
+  std::vector<hipEvent_t> evpool;
+};
+
+struct shk_ctx : ShkStageBufs {
   shk_config cfg;
   int dev;
-  hipStream_t stream;
   // geometry of this context (shard)
   uint64_t g_nslots;            // whole filter
   uint64_t q_lo, nslots, xnslots, nblocks, table_bytes;
@@ -55,24 +91,10 @@ struct shk_ctx {
   uint8_t *tab[2];
   uint64_t *fin[2];
   int cur;                      // which of tab[]/fin[] is live
-  uint8_t *d_text;
   uint8_t *d_up[2];             // shk_upload_text: two alternating buffers filled on a copy stream
   hipStream_t copy_stream;
   hipEvent_t up_done[2];
   int up_next, up_pending[2];
-  uint64_t *d_chunk_off, *d_chunk_len, *d_nlines, *d_reads_base;
-  uint64_t *d_rd_start, *d_rd_end;
-  uint16_t *d_rd_chunk;         // chunk (within the call) of every read
-  uint32_t *d_nkeys;
-  uint64_t *d_key_base;
-  uint64_t *d_words[2];
-  uint64_t *d_scalars;          // [0] nreads, [1] nwords, [2] scan total scratch, [3] marks
-  uint64_t *d_block_sums;
-  uint64_t *d_hist[4];          // per level: nbuckets*P (first level: times its window groups)
-  uint64_t *d_base_sub;         // first level with window groups: scanned bases of the (digit, group) sub-buckets
-  uint64_t *d_base[5];          // base[l]: bucket bases entering level l (base[nlevels] = region_base)
-  uint64_t *d_cursor;
-  uint32_t *d_tfb;
   uint32_t *d_summary;
   long long *d_tile_a, *d_tile_b, *d_tile_f;
   uint64_t *d_dump_offs;        // [nregions + 2] shk_dump: where every region's entries start in the output
@@ -89,25 +111,11 @@ struct shk_ctx {
   uint64_t *h_chist;            // pinned
   uint32_t chist_n;             // entries of h_chist valid from the last summary (0 = none)
   uint32_t sample_stride;       // sampled statistics pass before a deNoise point: every n-th region (<= 1: off)
-  uint32_t region_cap;          // how the partitioned words lie: 0 = d_base[nlevels] holds exact offsets; else region r owns the slot
-                                // [r * region_cap, ...) and d_base[nlevels][r] is its END (ShkRpLevel::slot_cap)
-  uint32_t slot_overflows;      // consecutive batches whose slotted last level overflowed; at 2 the slots are switched off
-  const uint64_t *stage2_b;     // shk_stage_words_pair: the second source of the first partition level (null = one source)
-  uint64_t stage2_na, stage2_nb;
-  int slots_off;
   uint32_t pt_lo, pt_split, pt_hi; int pt_valid; uint64_t pt_nprot;   // one-pass deNoise point in progress (shk_stage_point_*)
   const uint64_t *pt_words;     // its words (null: a round on its own, shk_stage_round_try)
   unsigned long long *d_counters;  // [SHK_NCOUNTERS]
-  uint32_t *d_err;
-  uint64_t *h_pinned;           // pinned mirror: counters [0, SHK_NCOUNTERS), err [40], scalars [41, 64)
   uint64_t max_reads;
-  // profiling
-  int prof_on;
-  double prof_ms[KP_N];
-  uint64_t prof_n[KP_N];
-  std::vector<PendingEvent> pending;
-  std::vector<hipEvent_t> evpool;
-  uint32_t last_err_bits;
+  int prof_on;                  // profiling: kernel times are recorded (ShkStageBufs::prof_ms)
   double new_frac;              // new distinct keys per presented k-mer in the last committed range (predicts crossings)
   int staged;                   // which d_words[] holds the partitioned words of shk_stage_words
   // one-pass deNoise point (denoise_fused): the intermediate table's (T, c), run lengths and free pointers; protected quotients
@@ -120,20 +128,21 @@ struct shk_ctx {
 
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "libshk: %s failed: %s (%s:%d)\n", #x, hipGetErrorString(e_), __FILE__, __LINE__); return SHK_ERR_HIP; } } while (0)
 
-static hipEvent_t ev_get(shk_ctx *c) {
+static hipEvent_t ev_get(ShkStageBufs *c) {
   if (!c->evpool.empty()) { hipEvent_t e = c->evpool.back(); c->evpool.pop_back(); return e; }
   hipEvent_t e; hipEventCreate(&e); return e;
 }
 struct ProfScope {
-  shk_ctx *c; int id; hipEvent_t a, b;
-  ProfScope(shk_ctx *c_, int id_) : c(c_), id(id_) {
-    if (c->prof_on) { a = ev_get(c); b = ev_get(c); hipEventRecord(a, c->stream); }
+  ShkStageBufs *c; int id; bool on; hipEvent_t a, b;
+  ProfScope(const shk_ctx *ctx, ShkStageBufs *c_, int id_) : c(c_), id(id_), on(ctx->prof_on != 0) {
+    if (on) { a = ev_get(c); b = ev_get(c); hipEventRecord(a, c->stream); }
   }
+  ProfScope(shk_ctx *ctx, int id_) : ProfScope(ctx, ctx, id_) {}
   ~ProfScope() {
-    if (c->prof_on) { hipEventRecord(b, c->stream); PendingEvent p = {id, a, b}; c->pending.push_back(p); }
+    if (on) { hipEventRecord(b, c->stream); PendingEvent p = {id, a, b}; c->pending.push_back(p); }
   }
 };
-static void prof_collect(shk_ctx *c) {
+static void prof_collect(ShkStageBufs *c) {
   for (size_t i = 0; i < c->pending.size(); i++) {
     float ms = 0;
     hipEventSynchronize(c->pending[i].b);
@@ -182,20 +191,76 @@ template <typename T> static int dmalloc(T **p, uint64_t n) {
 // ------------------------------------------------------------------ create / destroy
 static int ensure_chist(shk_ctx *c);
 static int point_alloc(shk_ctx *c);
-extern "C" int shk_create(const shk_config *cfg, shk_ctx **out) {
-  if (!cfg || !out) return SHK_ERR_ARG;
-  if (cfg->qb < 6 || cfg->qb > 40 || cfg->hb != cfg->qb + 8 || cfg->k < 1 || cfg->k > SHK_MAX_K) return SHK_ERR_ARG;
-  uint32_t ns = cfg->num_shards ? cfg->num_shards : 1;
-  if (ns & (ns - 1)) return SHK_ERR_ARG;
-  if (cfg->shard_index >= ns) return SHK_ERR_ARG;
-  if (cfg->hb + SHK_CHUNK_BITS > 64) return SHK_ERR_ARG;
-  shk_ctx *c = new shk_ctx();
+// buckets leaving partition level l (= entries of d_hist[l] without window groups, of d_base[l + 1])
+static uint64_t level_out(const shk_ctx *c, uint32_t l) { return (uint64_t)c->lv[l].nbuckets << c->lv[l].bits; }
+
+// The stream and the buffers of one front end, sized from the context's geometry. lent: the overlapped front end, whose
+// two words buffers and last-level bases are its slots' (set batch by batch; not allocated and not freed here).
+static int bufs_alloc(const shk_ctx *c, ShkStageBufs *b, bool lent) {
+  const uint64_t capk = c->cfg.max_batch_keys;
+  const uint32_t maxch = SHK_MAX_CHUNKS;
+  b->lent = lent;
+  b->slots_off = getenv("SHK_NO_SLOTS") ? 1 : 0;
+  // (a higher stream priority changes nothing measurable: the rebuild's small workgroups refill every CU as fast as they
+  // leave it, whatever the priority of the queue whose big workgroups are waiting)
+  if (lent) HIPCHK(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
+  else HIPCHK(hipStreamCreate(&b->stream));
+  if (dmalloc(&b->d_text, c->cfg.max_batch_bytes + 64)) return SHK_ERR_HIP;
+  if (dmalloc(&b->d_chunk_off, maxch) || dmalloc(&b->d_chunk_len, maxch) || dmalloc(&b->d_nlines, (uint64_t)maxch * SHK_PARSE_SEGS) ||
+      dmalloc(&b->d_reads_base, maxch + 1)) return SHK_ERR_HIP;
+  if (dmalloc(&b->d_rd_start, c->max_reads + 1) || dmalloc(&b->d_rd_end, c->max_reads + 1) ||
+      dmalloc(&b->d_nkeys, c->max_reads + 1) || dmalloc(&b->d_rd_chunk, c->max_reads + 1) || dmalloc(&b->d_key_base, c->max_reads + 2)) return SHK_ERR_HIP;
+  if (!lent && (dmalloc(&b->d_words[0], capk + 1) || dmalloc(&b->d_words[1], capk + 1))) return SHK_ERR_HIP;
+  if (dmalloc(&b->d_scalars, 64)) return SHK_ERR_HIP;
+  HIPCHK(hipMemsetAsync(b->d_scalars, 0, 64 * 8, b->stream));
+  {
+    uint64_t mx = capk > c->max_reads ? capk : c->max_reads;
+    uint64_t pw = 1ULL << c->rbits;
+    if (pw > mx) mx = pw;
+    if (dmalloc(&b->d_block_sums, mx / SHK_SCAN_TILE + 4 + 8192)) return SHK_ERR_HIP;
+  }
+  if (dmalloc(&b->d_base[0], 2)) return SHK_ERR_HIP;
+  for (uint32_t l = 0; l < c->nlevels; l++) {
+    const uint64_t n = level_out(c, l);
+    if (dmalloc(&b->d_hist[l], (n << c->lv[l].ng_log2) + 1)) return SHK_ERR_HIP;
+    if (!(lent && l + 1 == c->nlevels) && dmalloc(&b->d_base[l + 1], n + 2)) return SHK_ERR_HIP;
+    if (l == 0 && dmalloc(&b->d_base_sub, (n << c->lv[0].ng_log2) + 2)) return SHK_ERR_HIP;
+  }
+  { const uint64_t nb = level_out(c, c->nlevels - 1), first = 1ULL << (c->lv[0].bits + c->lv[0].ng_log2);
+    if (dmalloc(&b->d_cursor, (nb > first ? nb : first) + 2)) return SHK_ERR_HIP; }
+  if (dmalloc(&b->d_tfb, capk / SHK_RP_TILE + 2)) return SHK_ERR_HIP;
+  if (dmalloc(&b->d_err, 4)) return SHK_ERR_HIP;
+  HIPCHK(hipMemsetAsync(b->d_err, 0, 16, b->stream));
+  HIPCHK(hipHostMalloc((void **)&b->h_pinned, 64 * sizeof(uint64_t), hipHostMallocDefault));
+  HIPCHK(hipStreamSynchronize(b->stream));
+  return SHK_OK;
+}
+
+// (of a partly built object too: whatever bufs_alloc did not reach is null)
+static void bufs_free(const shk_ctx *c, ShkStageBufs *b) {
+  if (b->stream) hipStreamSynchronize(b->stream);
+  prof_collect(b);
+  for (size_t i = 0; i < b->evpool.size(); i++) hipEventDestroy(b->evpool[i]);
+  b->evpool.clear();
+  hipFree(b->d_text); hipFree(b->d_chunk_off); hipFree(b->d_chunk_len); hipFree(b->d_nlines); hipFree(b->d_reads_base);
+  hipFree(b->d_rd_start); hipFree(b->d_rd_end); hipFree(b->d_rd_chunk); hipFree(b->d_nkeys); hipFree(b->d_key_base); hipFree(b->d_scalars);
+  hipFree(b->d_block_sums); hipFree(b->d_base_sub); hipFree(b->d_cursor); hipFree(b->d_tfb); hipFree(b->d_err);
+  if (!b->lent) { hipFree(b->d_words[0]); hipFree(b->d_words[1]); }
+  for (uint32_t l = 0; l < 4; l++) hipFree(b->d_hist[l]);
+  for (uint32_t l = 0; l < 5; l++) if (!(b->lent && l == c->nlevels)) hipFree(b->d_base[l]);
+  hipHostFree(b->h_pinned);
+  if (b->stream) hipStreamDestroy(b->stream);
+  *b = ShkStageBufs();
+}
+
+// geometry, buffers and tables of a new context; whatever it leaves behind on failure is shk_destroy's
+static int create_init(shk_ctx *c, const shk_config *cfg) {
+  const uint32_t ns = cfg->num_shards ? cfg->num_shards : 1;
   c->cfg = *cfg;
   c->dev = cfg->device;
   HIPCHK(hipSetDevice(c->dev));
-  HIPCHK(hipStreamCreate(&c->stream));
   c->g_nslots = 1ULL << cfg->qb;
-  if (c->g_nslots / ns < 64) { delete c; return SHK_ERR_ARG; }
+  if (c->g_nslots / ns < 64) return SHK_ERR_ARG;
   c->nslots = c->g_nslots / ns;
   c->q_lo = c->nslots * cfg->shard_index;
   // qf_init geometry, gqf.c:2197-2198 (every shard keeps a full-size overflow tail)
@@ -206,10 +271,10 @@ extern "C" int shk_create(const shk_config *cfg, shk_ctx **out) {
   c->rbits = 0;
   while ((1u << c->rbits) < c->nregions) c->rbits++;
   const uint32_t mlb = cfg->max_level_bits ? cfg->max_level_bits : 10;
-  if (mlb > 10) { delete c; return SHK_ERR_ARG; }
-  c->nlevels = (c->rbits + mlb - 1) / mlb;
-  if (c->nlevels == 0) c->nlevels = 1;   // one region: a single pass still converts the words to 32-bit records
-  if (c->nlevels > 4) { delete c; return SHK_ERR_ARG; }
+  if (mlb > 10) return SHK_ERR_ARG;
+  const uint32_t nlevels = (c->rbits + mlb - 1) / mlb;
+  if (nlevels > 4) return SHK_ERR_ARG;
+  c->nlevels = nlevels ? nlevels : 1;   // one region: a single pass still converts the words to 32-bit records
   {
     uint32_t left = c->rbits, nb = 1;
     for (uint32_t l = 0; l < c->nlevels; l++) {
@@ -224,50 +289,20 @@ extern "C" int shk_create(const shk_config *cfg, shk_ctx **out) {
     if (c->lv[0].bits >= 2 && c->lv[0].bits <= 7 && !getenv("SHK_RP_NO_GROUPS")) c->lv[0].ng_log2 = 3;
   }
   c->threads = cfg->threads_per_group ? cfg->threads_per_group : 512;
-  if (c->threads < 64 || c->threads > 1024 || (c->threads & (c->threads - 1))) { delete c; return SHK_ERR_ARG; }
+  if (c->threads < 64 || c->threads > 1024 || (c->threads & (c->threads - 1))) return SHK_ERR_ARG;
   c->hash_groups = cfg->hash_groups ? cfg->hash_groups : 2048;
   c->rounds_left = cfg->num_denoise;
   c->max_reads = cfg->max_batch_reads ? cfg->max_batch_reads : cfg->max_batch_bytes / 16 + 1024;
-  const uint64_t capk = cfg->max_batch_keys;
-  const uint32_t maxch = SHK_MAX_CHUNKS;
+  { int rc = bufs_alloc(c, c, false); if (rc) return rc; }
   for (int i = 0; i < 2; i++) {
     if (dmalloc(&c->tab[i], c->table_bytes)) return SHK_ERR_HIP;
     if (dmalloc(&c->fin[i], (uint64_t)c->nregions + 2)) return SHK_ERR_HIP;
-    if (dmalloc(&c->d_words[i], capk + 1)) return SHK_ERR_HIP;
   }
-  if (dmalloc(&c->d_text, cfg->max_batch_bytes + 64)) return SHK_ERR_HIP;
-  if (dmalloc(&c->d_chunk_off, maxch) || dmalloc(&c->d_chunk_len, maxch) || dmalloc(&c->d_nlines, (uint64_t)maxch * SHK_PARSE_SEGS) ||
-      dmalloc(&c->d_reads_base, maxch + 1)) return SHK_ERR_HIP;
-  if (dmalloc(&c->d_rd_start, c->max_reads + 1) || dmalloc(&c->d_rd_end, c->max_reads + 1) ||
-      dmalloc(&c->d_nkeys, c->max_reads + 1) || dmalloc(&c->d_rd_chunk, c->max_reads + 1) || dmalloc(&c->d_key_base, c->max_reads + 2)) return SHK_ERR_HIP;
-  if (dmalloc(&c->d_scalars, 64)) return SHK_ERR_HIP;
-  HIPCHK(hipMemsetAsync(c->d_scalars, 0, 64 * 8, c->stream));
-  {
-    uint64_t mx = capk > c->max_reads ? capk : c->max_reads;
-    uint64_t pw = 1ULL << c->rbits;
-    if (pw > mx) mx = pw;
-    if (dmalloc(&c->d_block_sums, mx / SHK_SCAN_TILE + 4 + 8192)) return SHK_ERR_HIP;
-  }
-  {
-    uint64_t nb = 1;
-    if (dmalloc(&c->d_base[0], 2)) return SHK_ERR_HIP;
-    for (uint32_t l = 0; l < c->nlevels; l++) {
-      uint64_t n = nb << c->lv[l].bits;
-      if (dmalloc(&c->d_hist[l], (n << c->lv[l].ng_log2) + 1) || dmalloc(&c->d_base[l + 1], n + 2)) return SHK_ERR_HIP;
-      if (l == 0 && dmalloc(&c->d_base_sub, (n << c->lv[0].ng_log2) + 2)) return SHK_ERR_HIP;
-      nb = n;
-    }
-    { const uint64_t first = (1ULL << (c->lv[0].bits + c->lv[0].ng_log2));
-      if (dmalloc(&c->d_cursor, (nb > first ? nb : first) + 2)) return SHK_ERR_HIP; }
-  }
-  if (dmalloc(&c->d_tfb, capk / SHK_RP_TILE + 2)) return SHK_ERR_HIP;
   if (dmalloc(&c->d_summary, SHK_SUM_STRIDE * (uint64_t)c->nregions + 8)) return SHK_ERR_HIP;
   if (dmalloc(&c->d_dump_offs, (uint64_t)c->nregions + 2)) return SHK_ERR_HIP;
   c->merge_group = SHK_MERGE_GROUP;
   if (const char *mg = getenv("SHK_MERGE_GROUP")) { int v = atoi(mg); if (v == 64 || v == 128) c->merge_group = (uint32_t)v; }
-  // the sampled location of a deNoise point needs enough regions for the sample to mean something
-  c->region_cap = 0; c->slot_overflows = 0; c->slots_off = getenv("SHK_NO_SLOTS") ? 1 : 0;
-  c->stage2_b = nullptr; c->stage2_na = c->stage2_nb = 0;
+  // the sampled location of a deNoise point needs enough regions for the sample to mean something:
   // every 8th region; every 16th from 2^20 regions on (qb >= 28): a wrong guess costs one more one-pass point (18 ms at
   // qb 29), the sample 1.9 / 1.15 / 0.75 ms at stride 8 / 16 / 32; measured on the 12 points of the qb-29 bench: no wrong
   // guess at 8 and 16, one at 32 (its chance grows with sqrt(stride) / sqrt(new keys per batch))
@@ -278,144 +313,159 @@ extern "C" int shk_create(const shk_config *cfg, shk_ctx **out) {
   { uint64_t nt = c->nregions / SHK_RSCAN_TILE + 2;
     if (dmalloc(&c->d_tile_a, nt) || dmalloc(&c->d_tile_b, nt) || dmalloc(&c->d_tile_f, nt)) return SHK_ERR_HIP; }
   if (dmalloc(&c->d_counters, SHK_NCOUNTERS)) return SHK_ERR_HIP;
-  if (dmalloc(&c->d_err, 4)) return SHK_ERR_HIP;
-  HIPCHK(hipHostMalloc((void **)&c->h_pinned, 64 * sizeof(uint64_t), hipHostMallocDefault));
   HIPCHK(hipMemsetAsync(c->tab[0], 0, c->table_bytes + SHK_SLACK, c->stream));
   HIPCHK(hipMemsetAsync(c->tab[1], 0, c->table_bytes + SHK_SLACK, c->stream));
   HIPCHK(hipMemsetAsync(c->fin[0], 0, ((uint64_t)c->nregions + 2) * 8, c->stream));
   HIPCHK(hipMemsetAsync(c->fin[1], 0, ((uint64_t)c->nregions + 2) * 8, c->stream));
-  HIPCHK(hipMemsetAsync(c->d_err, 0, 16, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   // A context that is going to take deNoise rounds (its own, or as a shard of a filter that does) gets the buffers of the
   // first-chunk records and of the one-pass point now: allocating gigabytes inside a counting call is a synchronous trip
   // into the driver in the middle of the build (contexts without rounds never pay for them)
   if (cfg->num_denoise > 0 || cfg->num_shards > 1) {
-    if (ensure_chist(c) || point_alloc(c)) { shk_destroy(c); return SHK_ERR_HIP; }
+    if (ensure_chist(c) || point_alloc(c)) return SHK_ERR_HIP;
   }
   if (cfg->num_shards > 1 && !getenv("SHK_ROUTE_SINGLE_BUFFER")) {     // the two send buffers of shk_route_words, for the same reason
     for (int b = 0; b < 2; b++)
-      if (dmalloc(&c->d_send[b], c->cfg.max_batch_keys + 1)) { shk_destroy(c); return SHK_ERR_HIP; }
+      if (dmalloc(&c->d_send[b], c->cfg.max_batch_keys + 1)) return SHK_ERR_HIP;
   }
+  return SHK_OK;
+}
+
+extern "C" int shk_create(const shk_config *cfg, shk_ctx **out) {
+  if (!cfg || !out) return SHK_ERR_ARG;
+  if (cfg->qb < 6 || cfg->qb > 40 || cfg->hb != cfg->qb + 8 || cfg->k < 1 || cfg->k > SHK_MAX_K) return SHK_ERR_ARG;
+  uint32_t ns = cfg->num_shards ? cfg->num_shards : 1;
+  if (ns & (ns - 1)) return SHK_ERR_ARG;
+  if (cfg->shard_index >= ns) return SHK_ERR_ARG;
+  if (cfg->hb + SHK_CHUNK_BITS > 64) return SHK_ERR_ARG;
+  shk_ctx *c = new shk_ctx();
+  const int rc = create_init(c, cfg);
+  if (rc) { shk_destroy(c); return rc; }
   *out = c;
   return SHK_OK;
 }
 
+// (of a partly built context too: shk_create comes here from every failure)
 static void front_destroy(shk_ctx *c);
 extern "C" void shk_destroy(shk_ctx *c) {
   if (!c) return;
   hipSetDevice(c->dev);
   front_destroy(c);
-  hipStreamSynchronize(c->stream);
+  if (c->stream) hipStreamSynchronize(c->stream);
   if (c->copy_stream) {
     hipStreamSynchronize(c->copy_stream);
     for (int b = 0; b < 2; b++) { if (c->d_up[b]) hipFree(c->d_up[b]); if (c->up_done[b]) hipEventDestroy(c->up_done[b]); }
     hipStreamDestroy(c->copy_stream);
   }
-  if (getenv("SHK_STAMPS")) {
+  if (getenv("SHK_STAMPS") && c->d_scalars) {
     unsigned long long st[16];
     hipMemcpy(st, c->d_scalars + 16, sizeof(st), hipMemcpyDeviceToHost);
     static const char *nm[9] = {"stage+init", "fold keys", "old rank/select", "count sort", "merge pass", "scan+stats", "(unused)", "placement", "stores"};
     unsigned long long tot = 0; for (int i = 0; i < 9; i++) tot += st[i];
     for (int i = 0; i < 9; i++) fprintf(stderr, "SHK_STAMPS %-16s %6.2f %%\n", nm[i], tot ? 100.0 * st[i] / tot : 0.0);
   }
-  prof_collect(c);
-  for (size_t i = 0; i < c->evpool.size(); i++) hipEventDestroy(c->evpool[i]);
-  for (int i = 0; i < 2; i++) { hipFree(c->tab[i]); hipFree(c->fin[i]); hipFree(c->d_words[i]); if (c->d_send[i]) hipFree(c->d_send[i]); }
-  hipFree(c->d_text); hipFree(c->d_chunk_off); hipFree(c->d_chunk_len); hipFree(c->d_nlines); hipFree(c->d_reads_base);
-  hipFree(c->d_rd_start); hipFree(c->d_rd_end); hipFree(c->d_rd_chunk); hipFree(c->d_nkeys); hipFree(c->d_key_base); hipFree(c->d_scalars);
-  hipFree(c->d_block_sums);
-  hipFree(c->d_base[0]); hipFree(c->d_base_sub);
-  for (uint32_t l = 0; l < c->nlevels; l++) { hipFree(c->d_hist[l]); hipFree(c->d_base[l + 1]); }
-  if (c->d_isum) { hipFree(c->d_isum); hipFree(c->d_ilens); hipFree(c->d_fin_i); hipFree(c->d_prot); }
-  hipFree(c->d_spill); hipFree(c->d_over_list); if (c->d_newchunks) { hipFree(c->d_newchunks); hipFree(c->d_chist); hipHostFree(c->h_chist); } hipFree(c->d_cursor); hipFree(c->d_tfb); hipFree(c->d_summary); hipFree(c->d_dump_offs); hipFree(c->d_tile_a); hipFree(c->d_tile_b); hipFree(c->d_tile_f); hipFree(c->d_counters); hipFree(c->d_err);
-  hipHostFree(c->h_pinned);
-  hipStreamDestroy(c->stream);
+  for (int i = 0; i < 2; i++) { hipFree(c->tab[i]); hipFree(c->fin[i]); hipFree(c->d_send[i]); }
+  hipFree(c->d_isum); hipFree(c->d_ilens); hipFree(c->d_fin_i); hipFree(c->d_prot);
+  hipFree(c->d_newchunks); hipFree(c->d_chist); hipHostFree(c->h_chist);
+  hipFree(c->d_spill); hipFree(c->d_over_list); hipFree(c->d_summary); hipFree(c->d_dump_offs); hipFree(c->d_tile_a); hipFree(c->d_tile_b); hipFree(c->d_tile_f); hipFree(c->d_counters);
+  bufs_free(c, c);
   delete c;
 }
 
 // ------------------------------------------------------------------ helpers
 // exclusive scan of in[0..n) (n on the host, or *n_dev on the device with n_max as bound)
 template <typename T>
-static int run_scan(shk_ctx *c, const T *in, uint64_t n_max, const uint64_t *n_dev, uint64_t *out, uint64_t *sums = nullptr) {
+static int run_scan(const shk_ctx *c, ShkStageBufs *b, const T *in, uint64_t n_max, const uint64_t *n_dev, uint64_t *out, uint64_t *sums = nullptr) {
   // sums: n_max / SHK_SCAN_TILE + 2 words of scratch; the context's own fits the batch sizes it was created for
-  ProfScope ps(c, KP_SCAN);
-  if (!sums) sums = c->d_block_sums;
+  ProfScope ps(c, b, KP_SCAN);
+  if (!sums) sums = b->d_block_sums;
   const uint32_t nb = (uint32_t)(n_max / SHK_SCAN_TILE + 1);
-  hipLaunchKernelGGL((k_scan_reduce<T>), dim3(nb), dim3(c->threads), 0, c->stream, in, n_max, n_dev, sums);
-  hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(c->threads), 0, c->stream, sums, (uint64_t)nb, c->d_scalars + 2);
-  hipLaunchKernelGGL((k_scan_apply<T>), dim3(nb), dim3(c->threads), 0, c->stream, in, n_max, n_dev, sums,
-                     c->d_scalars + 2, out);
+  hipLaunchKernelGGL((k_scan_reduce<T>), dim3(nb), dim3(c->threads), 0, b->stream, in, n_max, n_dev, sums);
+  hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(c->threads), 0, b->stream, sums, (uint64_t)nb, b->d_scalars + 2);
+  hipLaunchKernelGGL((k_scan_apply<T>), dim3(nb), dim3(c->threads), 0, b->stream, in, n_max, n_dev, sums,
+                     b->d_scalars + 2, out);
   HIPCHK(hipGetLastError());
   return 0;
 }
 
-static int fetch_err(shk_ctx *c, uint32_t *bits) {
-  HIPCHK(hipMemcpyAsync(c->h_pinned + 40, c->d_err, 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  *bits = *(uint32_t *)(c->h_pinned + 40);
-  if (*bits) c->last_err_bits = *bits;
-  if (*bits) hipMemsetAsync(c->d_err, 0, 16, c->stream);
+static int fetch_err(ShkStageBufs *b, uint32_t *bits) {
+  HIPCHK(hipMemcpyAsync(b->h_pinned + 40, b->d_err, 4, hipMemcpyDeviceToHost, b->stream));
+  HIPCHK(hipStreamSynchronize(b->stream));
+  *bits = *(uint32_t *)(b->h_pinned + 40);
+  if (*bits) b->last_err_bits = *bits;
+  if (*bits) hipMemsetAsync(b->d_err, 0, 16, b->stream);
   return 0;
 }
 
-// text + chunk table -> key words in d_words[0]; d_scalars[1] = #words
+// Device text that is a buffer of shk_upload_text whose copy may still be running: `stream` waits for it. For the entry
+// points, on the caller's thread (the stage functions leave the context alone).
+static int upload_wait(shk_ctx *c, const void *text, int on_device, hipStream_t stream) {
+  for (int u = 0; on_device && u < 2; u++)
+    if (c->d_up[u] && text == (const void *)c->d_up[u] && c->up_pending[u]) { HIPCHK(hipStreamWaitEvent(stream, c->up_done[u], 0)); c->up_pending[u] = 0; }
+  return SHK_OK;
+}
+
+// chunk i of a call is labelled chunk_first + i * chunk_mul: do the labels of nchunks chunks fit?
+static bool chunk_labels_ok(uint32_t nchunks, uint32_t chunk_first, uint32_t chunk_mul) {
+  return nchunks != 0 && nchunks <= SHK_MAX_CHUNKS && chunk_first + (uint64_t)(nchunks - 1) * chunk_mul < SHK_MAX_CHUNKS;
+}
+
 // text -> extents of every read (d_rd_start, d_rd_end, d_rd_chunk); *dtext_out = where the text is on the device
-static int parse_stage(shk_ctx *c, const void *text, int on_device, uint64_t text_bytes, const uint64_t *chunk_off,
+static int parse_stage(const shk_ctx *c, ShkStageBufs *b, const void *text, int on_device, uint64_t text_bytes, const uint64_t *chunk_off,
                        const uint64_t *chunk_len, uint32_t nchunks, const uint8_t **dtext_out, uint64_t *nreads_out) {
   for (uint32_t i = 0; i < nchunks; i++)
     if (chunk_off[i] + chunk_len[i] > text_bytes) return SHK_ERR_ARG;
   const uint8_t *dtext;
   if (on_device) {
     dtext = (const uint8_t *)text;
-    for (int b = 0; b < 2; b++)   // a buffer of shk_upload_text whose copy may still be running
-      if (c->d_up[b] && dtext == c->d_up[b] && c->up_pending[b]) { HIPCHK(hipStreamWaitEvent(c->stream, c->up_done[b], 0)); c->up_pending[b] = 0; }
   } else {
     if (text_bytes > c->cfg.max_batch_bytes) return SHK_ERR_BATCH;
-    HIPCHK(hipMemcpyAsync(c->d_text, text, text_bytes, hipMemcpyHostToDevice, c->stream));
-    dtext = c->d_text;
+    HIPCHK(hipMemcpyAsync(b->d_text, text, text_bytes, hipMemcpyHostToDevice, b->stream));
+    dtext = b->d_text;
   }
-  HIPCHK(hipMemcpyAsync(c->d_chunk_off, chunk_off, nchunks * 8, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(c->d_chunk_len, chunk_len, nchunks * 8, hipMemcpyHostToDevice, c->stream));
-  { ProfScope ps(c, KP_COUNT_LINES);
-    hipLaunchKernelGGL(k_count_lines, dim3(nchunks * SHK_PARSE_SEGS), dim3(c->threads), 0, c->stream, dtext, c->d_chunk_off, c->d_chunk_len, c->d_nlines); }
-  { ProfScope ps(c, KP_SCAN_CHUNKS);
-    hipLaunchKernelGGL(k_scan_chunks, dim3(1), dim3(c->threads), 0, c->stream, c->d_nlines, nchunks, c->d_reads_base, c->d_scalars + 0); }
+  HIPCHK(hipMemcpyAsync(b->d_chunk_off, chunk_off, nchunks * 8, hipMemcpyHostToDevice, b->stream));
+  HIPCHK(hipMemcpyAsync(b->d_chunk_len, chunk_len, nchunks * 8, hipMemcpyHostToDevice, b->stream));
+  { ProfScope ps(c, b, KP_COUNT_LINES);
+    hipLaunchKernelGGL(k_count_lines, dim3(nchunks * SHK_PARSE_SEGS), dim3(c->threads), 0, b->stream, dtext, b->d_chunk_off, b->d_chunk_len, b->d_nlines); }
+  { ProfScope ps(c, b, KP_SCAN_CHUNKS);
+    hipLaunchKernelGGL(k_scan_chunks, dim3(1), dim3(c->threads), 0, b->stream, b->d_nlines, nchunks, b->d_reads_base, b->d_scalars + 0); }
   // the read arrays are sized by max_reads: the count is checked on the host below
-  HIPCHK(hipMemcpyAsync(c->h_pinned + 41, c->d_scalars, 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  const uint64_t nreads = c->h_pinned[41];
+  HIPCHK(hipMemcpyAsync(b->h_pinned + 41, b->d_scalars, 8, hipMemcpyDeviceToHost, b->stream));
+  HIPCHK(hipStreamSynchronize(b->stream));
+  const uint64_t nreads = b->h_pinned[41];
   if (nreads > c->max_reads) return SHK_ERR_BATCH;
-  { ProfScope ps(c, KP_EMIT_READS);
-    hipLaunchKernelGGL(k_emit_reads, dim3(nchunks * SHK_PARSE_SEGS), dim3(c->threads), 0, c->stream, dtext, c->d_chunk_off, c->d_chunk_len,
-                       c->d_reads_base, c->d_nlines, c->d_rd_start, c->d_rd_end, c->d_rd_chunk); }
+  { ProfScope ps(c, b, KP_EMIT_READS);
+    hipLaunchKernelGGL(k_emit_reads, dim3(nchunks * SHK_PARSE_SEGS), dim3(c->threads), 0, b->stream, dtext, b->d_chunk_off, b->d_chunk_len,
+                       b->d_reads_base, b->d_nlines, b->d_rd_start, b->d_rd_end, b->d_rd_chunk); }
   *dtext_out = dtext;
   *nreads_out = nreads;
   return SHK_OK;
 }
 
-static int hash_stage(shk_ctx *c, const void *text, int on_device, uint64_t text_bytes, const uint64_t *chunk_off,
+// text + chunk table -> key words in d_words[0]; d_scalars[1] = #words
+static int hash_stage(const shk_ctx *c, ShkStageBufs *b, const void *text, int on_device, uint64_t text_bytes, const uint64_t *chunk_off,
                       const uint64_t *chunk_len, uint32_t nchunks, uint32_t chunk_first, uint32_t chunk_mul, bool hist0 = false) {
   // chunk i of this call is labelled chunk_first + i * chunk_mul; hist0: the hash kernel also fills the first partition
   // level's histogram (d_hist[0]), see partition_stage
-  if (hist0) HIPCHK(hipMemsetAsync(c->d_hist[0], 0, (1ULL << (c->lv[0].bits + c->lv[0].ng_log2)) * 8, c->stream));
-  if (nchunks == 0 || nchunks > SHK_MAX_CHUNKS || chunk_first + (uint64_t)(nchunks - 1) * chunk_mul >= SHK_MAX_CHUNKS) return SHK_ERR_BATCH;
+  if (hist0) HIPCHK(hipMemsetAsync(b->d_hist[0], 0, (1ULL << (c->lv[0].bits + c->lv[0].ng_log2)) * 8, b->stream));
+  if (!chunk_labels_ok(nchunks, chunk_first, chunk_mul)) return SHK_ERR_BATCH;
   const uint8_t *dtext;
   uint64_t nreads;
-  { int rc = parse_stage(c, text, on_device, text_bytes, chunk_off, chunk_len, nchunks, &dtext, &nreads); if (rc) return rc; }
+  { int rc = parse_stage(c, b, text, on_device, text_bytes, chunk_off, chunk_len, nchunks, &dtext, &nreads); if (rc) return rc; }
   uint32_t groups = c->hash_groups;
   { uint64_t need = nreads / (c->threads / SHK_WAVE) + 1; if (need < groups) groups = (uint32_t)need; }
-  { ProfScope ps(c, KP_COUNT_KEYS);       // (one thread per read)
+  { ProfScope ps(c, b, KP_COUNT_KEYS);       // (one thread per read)
     const uint64_t blocks = nreads / 256 + 1;
-    hipLaunchKernelGGL(k_count_keys, dim3((uint32_t)(blocks < (1u << 20) ? blocks : (1u << 20))), dim3(256), 0, c->stream, dtext, c->d_rd_start, c->d_rd_end,
-                       c->d_scalars + 0, c->cfg.k, c->d_nkeys, c->d_err); }
-  if (run_scan<uint32_t>(c, c->d_nkeys, nreads, nullptr, c->d_key_base)) return SHK_ERR_HIP;
+    hipLaunchKernelGGL(k_count_keys, dim3((uint32_t)(blocks < (1u << 20) ? blocks : (1u << 20))), dim3(256), 0, b->stream, dtext, b->d_rd_start, b->d_rd_end,
+                       b->d_scalars + 0, c->cfg.k, b->d_nkeys, b->d_err); }
+  if (run_scan<uint32_t>(c, b, b->d_nkeys, nreads, nullptr, b->d_key_base)) return SHK_ERR_HIP;
   // total = key_base[nreads] -> d_scalars[1]
-  HIPCHK(hipMemcpyAsync(c->d_scalars + 1, c->d_key_base + nreads, 8, hipMemcpyDeviceToDevice, c->stream));
-  { ProfScope ps(c, KP_HASH);
+  HIPCHK(hipMemcpyAsync(b->d_scalars + 1, b->d_key_base + nreads, 8, hipMemcpyDeviceToDevice, b->stream));
+  { ProfScope ps(c, b, KP_HASH);
     const uint32_t ht = c->threads < SHK_HASH_WAVES * SHK_WAVE ? c->threads : SHK_HASH_WAVES * SHK_WAVE;
-    hipLaunchKernelGGL(k_hash_reads, dim3(groups * (c->threads / ht)), dim3(ht), 0, c->stream, dtext, c->d_rd_start, c->d_rd_end,
-                       c->d_scalars + 0, c->d_rd_chunk, chunk_first, chunk_mul, c->d_key_base, c->cfg.k, c->cfg.hb,
-                       c->d_words[0], c->cfg.max_batch_keys, c->d_err, hist0 ? c->d_hist[0] : nullptr, c->lv[0].shift, c->lv[0].bits, c->q_lo, c->lv[0].ng_log2); }
+    hipLaunchKernelGGL(k_hash_reads, dim3(groups * (c->threads / ht)), dim3(ht), 0, b->stream, dtext, b->d_rd_start, b->d_rd_end,
+                       b->d_scalars + 0, b->d_rd_chunk, chunk_first, chunk_mul, b->d_key_base, c->cfg.k, c->cfg.hb,
+                       b->d_words[0], c->cfg.max_batch_keys, b->d_err, hist0 ? b->d_hist[0] : nullptr, c->lv[0].shift, c->lv[0].bits, c->q_lo, c->lv[0].ng_log2); }
   HIPCHK(hipGetLastError());
   return SHK_OK;
 }
@@ -423,87 +473,89 @@ static int hash_stage(shk_ctx *c, const void *text, int on_device, uint64_t text
 // 2-bit staging of the batch's reads for the roll kernels (k_pack_reads), in `buf` = a buffer of max_batch_keys words that
 // nothing else uses until the roll kernels are done. Leaves A.pk null (text path for every read) when the buffer cannot
 // hold the batch's units or SHK_NO_PACK is set (measurement).
-static int pack_stage(shk_ctx *c, ShkRollArgs &A, uint64_t nreads, uint64_t text_bytes, uint64_t *buf) {
+static int pack_stage(const shk_ctx *c, ShkStageBufs *b, ShkRollArgs &A, uint64_t nreads, uint64_t text_bytes, uint64_t *buf) {
   A.pk = nullptr; A.pk_base = nullptr; A.pk_flag = nullptr;
   // units <= sum over reads of (len / 64 + 1) <= text_bytes / 64 + nreads when no two chunks overlap (k_pack_reads leaves
   // the reads that do not fit on the text path); 16 bytes of slack for the roll kernels' 16-byte fetches
   const uint64_t cap_units = c->cfg.max_batch_keys / 2 > 1 ? c->cfg.max_batch_keys / 2 - 1 : 0;
   if (getenv("SHK_NO_PACK") || text_bytes / 64 + nreads + 1 > cap_units) return SHK_OK;
-  ProfScope ps(c, KP_PACK);
+  ProfScope ps(c, b, KP_PACK);
   const uint32_t t = c->threads < 256 ? c->threads : 256;
   { const uint64_t blocks = nreads / t + 1;
-    hipLaunchKernelGGL(k_pack_count, dim3((uint32_t)(blocks < 4096 ? blocks : 4096)), dim3(t), 0, c->stream, (const uint64_t *)c->d_rd_start,
-                       (const uint64_t *)c->d_rd_end, (const uint64_t *)(c->d_scalars + 0), c->cfg.k, c->d_nkeys); }
-  if (run_scan<uint32_t>(c, c->d_nkeys, nreads, nullptr, c->d_key_base)) return SHK_ERR_HIP;
+    hipLaunchKernelGGL(k_pack_count, dim3((uint32_t)(blocks < 4096 ? blocks : 4096)), dim3(t), 0, b->stream, (const uint64_t *)b->d_rd_start,
+                       (const uint64_t *)b->d_rd_end, (const uint64_t *)(b->d_scalars + 0), c->cfg.k, b->d_nkeys); }
+  if (run_scan<uint32_t>(c, b, b->d_nkeys, nreads, nullptr, b->d_key_base)) return SHK_ERR_HIP;
   { const uint64_t blocks = nreads * 4 / t + 1;
-    hipLaunchKernelGGL(k_pack_reads, dim3((uint32_t)(blocks < 16384 ? blocks : 16384)), dim3(t), 0, c->stream, A.text, A.safe_end,
-                       (const uint64_t *)c->d_rd_start, (const uint64_t *)c->d_rd_end, (const uint64_t *)(c->d_scalars + 0),
-                       (const uint64_t *)c->d_key_base, c->d_nkeys, (ShkQuad *)buf, cap_units); }
-  A.pk = (const ShkQuad *)buf; A.pk_base = c->d_key_base; A.pk_flag = c->d_nkeys;
+    hipLaunchKernelGGL(k_pack_reads, dim3((uint32_t)(blocks < 16384 ? blocks : 16384)), dim3(t), 0, b->stream, A.text, A.safe_end,
+                       (const uint64_t *)b->d_rd_start, (const uint64_t *)b->d_rd_end, (const uint64_t *)(b->d_scalars + 0),
+                       (const uint64_t *)b->d_key_base, b->d_nkeys, (ShkQuad *)buf, cap_units); }
+  A.pk = (const ShkQuad *)buf; A.pk_base = b->d_key_base; A.pk_flag = b->d_nkeys;
   return SHK_OK;
+}
+
+// What the roll kernels take from the parse and the configuration; the caller adds the digits (q_lo, dig_*, hist*), the
+// cursors and the output.
+static void roll_args(const shk_ctx *c, ShkStageBufs *b, ShkRollArgs &A, const uint8_t *dtext, uint64_t text_bytes,
+                      uint32_t chunk_first, uint32_t chunk_mul) {
+  A.text = dtext; A.safe_end = (text_bytes + 15) & ~15ULL;
+  A.rd_start = b->d_rd_start; A.rd_end = b->d_rd_end; A.nreads_p = b->d_scalars + 0; A.rd_chunk = b->d_rd_chunk;
+  A.chunk_first = chunk_first; A.chunk_mul = chunk_mul; A.k = c->cfg.k; A.hb = c->cfg.hb;
+  A.cap = c->cfg.max_batch_keys; A.err = b->d_err;
+}
+// wide: A.hist_bits may exceed 10 (up to 14: two levels' digits together)
+static void launch_roll_hist(const shk_ctx *c, ShkStageBufs *b, const ShkRollArgs &A, uint64_t nreads, bool wide) {
+  const bool small = c->threads < 512;     // (small workgroups: the CPU emulator build of the tests)
+  const uint32_t t = small ? 64 : wide ? 512 : 256, max_blocks = small ? 64 : wide ? 1024 : 4096;
+  const uint64_t blocks = nreads / t + 1;
+  const dim3 grid((uint32_t)(blocks < max_blocks ? blocks : max_blocks));
+  if (small && wide) hipLaunchKernelGGL((k_roll_hist<14, 64>), grid, dim3(64), 0, b->stream, A);
+  else if (small) hipLaunchKernelGGL((k_roll_hist<10, 64>), grid, dim3(64), 0, b->stream, A);
+  else if (wide) hipLaunchKernelGGL((k_roll_hist<14, 512>), grid, dim3(512), 0, b->stream, A);
+  else hipLaunchKernelGGL((k_roll_hist<10, 256>), grid, dim3(256), 0, b->stream, A);
+}
+static void launch_roll_scatter(const shk_ctx *c, ShkStageBufs *b, const ShkRollArgs &A, uint64_t nreads) {
+  ProfScope ps(c, b, KP_ROLL_SCATTER);
+  if (c->threads >= 512) {
+    const uint64_t blocks = nreads / 1024 + 1;
+    hipLaunchKernelGGL((k_roll_scatter<1024, 1>), dim3((uint32_t)(blocks < 512 ? blocks : 512)), dim3(1024), 0, b->stream, A);
+  } else {          // (small workgroups: the CPU emulator build of the tests)
+    const uint64_t blocks = nreads / 64 + 1;
+    hipLaunchKernelGGL((k_roll_scatter<64, 4>), dim3((uint32_t)(blocks < 64 ? blocks : 64)), dim3(64), 0, b->stream, A);
+  }
 }
 
 // text + chunk table -> key words in d_words[0], partitioned by the first region digit; d_base[1] = bucket bases,
 // d_scalars[1] = #words (roll_kernels.hip). For contexts with at least two partition levels.
 static bool roll_path(const shk_ctx *c) { return c->nlevels >= 2 && (c->q_lo & (SHK_REGION - 1)) == 0 && !getenv("SHK_NO_ROLL"); }
-static int roll_stage(shk_ctx *c, const void *text, int on_device, uint64_t text_bytes, const uint64_t *chunk_off,
+static int roll_stage(const shk_ctx *c, ShkStageBufs *b, const void *text, int on_device, uint64_t text_bytes, const uint64_t *chunk_off,
                       const uint64_t *chunk_len, uint32_t nchunks, uint32_t chunk_first, uint32_t chunk_mul, bool *level1_hist_ready) {
-  if (nchunks == 0 || nchunks > SHK_MAX_CHUNKS || chunk_first + (uint64_t)(nchunks - 1) * chunk_mul >= SHK_MAX_CHUNKS) return SHK_ERR_BATCH;
+  if (!chunk_labels_ok(nchunks, chunk_first, chunk_mul)) return SHK_ERR_BATCH;
   const uint8_t *dtext;
   uint64_t nreads;
-  { int rc = parse_stage(c, text, on_device, text_bytes, chunk_off, chunk_len, nchunks, &dtext, &nreads); if (rc) return rc; }
+  { int rc = parse_stage(c, b, text, on_device, text_bytes, chunk_off, chunk_len, nchunks, &dtext, &nreads); if (rc) return rc; }
   const uint64_t P = 1ULL << c->lv[0].bits;
   // the first two levels' digits together, when they fit the histogram pass's LDS bins
   const uint32_t cb = c->lv[0].bits + c->lv[1].bits;
   const bool two = cb <= 14 && !getenv("SHK_ROLL_HIST1");
   *level1_hist_ready = two;
-  if (two) HIPCHK(hipMemsetAsync(c->d_hist[1], 0, (1ULL << cb) * 8, c->stream));
-  else HIPCHK(hipMemsetAsync(c->d_hist[0], 0, P * 8, c->stream));
+  if (two) HIPCHK(hipMemsetAsync(b->d_hist[1], 0, (1ULL << cb) * 8, b->stream));
+  else HIPCHK(hipMemsetAsync(b->d_hist[0], 0, P * 8, b->stream));
   ShkRollArgs A;
-  A.text = dtext; A.safe_end = (text_bytes + 15) & ~15ULL;
-  A.rd_start = c->d_rd_start; A.rd_end = c->d_rd_end; A.nreads_p = c->d_scalars + 0; A.rd_chunk = c->d_rd_chunk;
-  A.chunk_first = chunk_first; A.chunk_mul = chunk_mul; A.k = c->cfg.k; A.hb = c->cfg.hb; A.q_lo = c->q_lo;
+  roll_args(c, b, A, dtext, text_bytes, chunk_first, chunk_mul);
+  A.q_lo = c->q_lo;
   A.dig_shift = c->lv[0].shift; A.dig_bits = c->lv[0].bits;
-  A.hist = two ? c->d_hist[1] : c->d_hist[0]; A.hist_shift = two ? c->lv[1].shift : c->lv[0].shift; A.hist_bits = two ? cb : c->lv[0].bits;
-  A.cursor = c->d_cursor; A.out = c->d_words[0]; A.cap = c->cfg.max_batch_keys; A.err = c->d_err;
-  { int rc = pack_stage(c, A, nreads, text_bytes, c->d_words[1]); if (rc) return rc; }     // (d_words[1]: the partition's other buffer, idle until its second level)
-  { ProfScope ps(c, KP_ROLL_HIST);
-    if (two && c->threads >= 512) {
-      const uint64_t blocks = nreads / 512 + 1;
-      hipLaunchKernelGGL((k_roll_hist<14, 512>), dim3((uint32_t)(blocks < 1024 ? blocks : 1024)), dim3(512), 0, c->stream, A);
-    } else if (two) {     // (small workgroups: the CPU emulator build of the tests)
-      const uint64_t blocks = nreads / 64 + 1;
-      hipLaunchKernelGGL((k_roll_hist<14, 64>), dim3((uint32_t)(blocks < 64 ? blocks : 64)), dim3(64), 0, c->stream, A);
-    } else {
-      const uint64_t blocks = nreads / 256 + 1;
-      hipLaunchKernelGGL((k_roll_hist<10, 256>), dim3((uint32_t)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, c->stream, A);
-    }
-    if (two) hipLaunchKernelGGL(k_roll_fold, dim3((uint32_t)(P / 256 + 1)), dim3(256), 0, c->stream, (const uint64_t *)c->d_hist[1], (uint32_t)P,
-                                1u << c->lv[1].bits, c->d_hist[0]); }
+  A.hist = two ? b->d_hist[1] : b->d_hist[0]; A.hist_shift = two ? c->lv[1].shift : c->lv[0].shift; A.hist_bits = two ? cb : c->lv[0].bits;
+  A.cursor = b->d_cursor; A.out = b->d_words[0];
+  { int rc = pack_stage(c, b, A, nreads, text_bytes, b->d_words[1]); if (rc) return rc; }     // (d_words[1]: the partition's other buffer, idle until its second level)
+  { ProfScope ps(c, b, KP_ROLL_HIST);
+    launch_roll_hist(c, b, A, nreads, two);
+    if (two) hipLaunchKernelGGL(k_roll_fold, dim3((uint32_t)(P / 256 + 1)), dim3(256), 0, b->stream, (const uint64_t *)b->d_hist[1], (uint32_t)P,
+                                1u << c->lv[1].bits, b->d_hist[0]); }
   // bucket bases = exclusive scan of the digit counts; its total is the number of key words
-  if (run_scan<uint64_t>(c, c->d_hist[0], P, nullptr, c->d_base[1])) return SHK_ERR_HIP;
-  HIPCHK(hipMemcpyAsync(c->d_scalars + 1, c->d_base[1] + P, 8, hipMemcpyDeviceToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(c->d_cursor, c->d_base[1], P * 8, hipMemcpyDeviceToDevice, c->stream));
-  { ProfScope ps(c, KP_ROLL_SCATTER);
-    const char *nqe = getenv("SHK_ROLL_NQ");            // (measurement: 16-byte quads fetched at a time per stream)
-    const int nq = nqe ? atoi(nqe) : 1;
-    const char *te = getenv("SHK_ROLL_T");             // (measurement: threads per workgroup = keys per window / 16)
-    const int rt = te ? atoi(te) : 1024;
-    if (c->threads >= 512 && rt == 512) {
-      const uint64_t blocks = nreads / 512 + 1;
-      hipLaunchKernelGGL((k_roll_scatter<512, 1>), dim3((uint32_t)(blocks < 1024 ? blocks : 1024)), dim3(512), 0, c->stream, A);
-    } else if (c->threads >= 512 && rt == 256) {
-      const uint64_t blocks = nreads / 256 + 1;
-      hipLaunchKernelGGL((k_roll_scatter<256, 1>), dim3((uint32_t)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, c->stream, A);
-    } else if (c->threads >= 512) {
-      const uint64_t blocks = nreads / 1024 + 1;
-      const dim3 grid((uint32_t)(blocks < 512 ? blocks : 512));
-      if (nq == 1) hipLaunchKernelGGL((k_roll_scatter<1024, 1>), grid, dim3(1024), 0, c->stream, A);
-      else hipLaunchKernelGGL((k_roll_scatter<1024, 2>), grid, dim3(1024), 0, c->stream, A);
-    } else {          // (small workgroups: the CPU emulator build of the tests)
-      const uint64_t blocks = nreads / 64 + 1;
-      hipLaunchKernelGGL((k_roll_scatter<64, 4>), dim3((uint32_t)(blocks < 64 ? blocks : 64)), dim3(64), 0, c->stream, A);
-    } }
+  if (run_scan<uint64_t>(c, b, b->d_hist[0], P, nullptr, b->d_base[1])) return SHK_ERR_HIP;
+  HIPCHK(hipMemcpyAsync(b->d_scalars + 1, b->d_base[1] + P, 8, hipMemcpyDeviceToDevice, b->stream));
+  HIPCHK(hipMemcpyAsync(b->d_cursor, b->d_base[1], P * 8, hipMemcpyDeviceToDevice, b->stream));
+  launch_roll_scatter(c, b, A, nreads);
   HIPCHK(hipGetLastError());
   return SHK_OK;
 }
@@ -513,28 +565,28 @@ static int roll_stage(shk_ctx *c, const void *text, int on_device, uint64_t text
 // (ext != null: the first level reads the caller's buffer instead of d_words[src])
 // first_level = 1: the words in d_words[src] are partitioned by the first digit already and d_base[1] holds the bucket
 // bases (roll_stage)
-static int partition_stage(shk_ctx *c, int src, uint64_t nmax, int *dst, const uint64_t *ext = nullptr, bool hist0_ready = false,
+static int partition_stage(const shk_ctx *c, ShkStageBufs *b, int src, uint64_t nmax, int *dst, const uint64_t *ext = nullptr, bool hist0_ready = false,
                            uint32_t first_level = 0, bool hist1_ready = false) {
-  const uint64_t *n_p = c->d_scalars + 1;
-  { ProfScope ps(c, KP_RP_PREP);
-    hipLaunchKernelGGL(k_rp_base1, dim3(1), dim3(64), 0, c->stream, n_p, c->d_base[0]); }
+  const uint64_t *n_p = b->d_scalars + 1;
+  { ProfScope ps(c, b, KP_RP_PREP);
+    hipLaunchKernelGGL(k_rp_base1, dim3(1), dim3(64), 0, b->stream, n_p, b->d_base[0]); }
   const uint32_t nwin = (uint32_t)(nmax / SHK_RP_TILE + 1);
-  const uint64_t *in = ext ? ext : c->d_words[src];
+  const uint64_t *in = ext ? ext : b->d_words[src];
   int cur = ext ? 1 : src;   // the buffer `in` occupies (an external source leaves both free: write to d_words[0] first)
-  c->region_cap = 0;
+  b->region_cap = 0;
   // shk_stage_words_pair: the first level reads TWO buffers (the words a shard kept for itself, where the routing left them,
   // and the words it received): both are counted into one histogram and scattered with one set of cursors. Their
   // lengths and one-bucket base arrays live in d_scalars[40..45].
-  const uint64_t *in2 = (ext && first_level == 0) ? c->stage2_b : nullptr;
-  const uint64_t n_a = in2 ? c->stage2_na : nmax, n_b = in2 ? c->stage2_nb : 0;
+  const uint64_t *in2 = (ext && first_level == 0) ? b->stage2_b : nullptr;
+  const uint64_t n_a = in2 ? b->stage2_na : nmax, n_b = in2 ? b->stage2_nb : 0;
   for (uint32_t l = first_level; l < c->nlevels; l++) {
     const uint64_t nb = c->lv[l].nbuckets, P = 1ULL << c->lv[l].bits;
     // the sources of this level: (words, their number on the device, their bucket bases, their number on the host)
-    struct Src { const uint64_t *w, *n_p, *base; uint64_t n; } srcs[2] = {{in, n_p, c->d_base[l], nmax}, {nullptr, nullptr, nullptr, 0}};
+    struct Src { const uint64_t *w, *n_p, *base; uint64_t n; } srcs[2] = {{in, n_p, b->d_base[l], nmax}, {nullptr, nullptr, nullptr, 0}};
     int nsrc = 1;
     if (l == 0 && in2) {
-      srcs[0] = {in, c->d_scalars + 40, c->d_scalars + 42, n_a};
-      srcs[1] = {in2, c->d_scalars + 41, c->d_scalars + 44, n_b};
+      srcs[0] = {in, b->d_scalars + 40, b->d_scalars + 42, n_a};
+      srcs[1] = {in2, b->d_scalars + 41, b->d_scalars + 44, n_b};
       nsrc = 2;
     }
     // Last level: fixed-capacity region slots instead of a histogram pass over the keys + scan, when the output buffer
@@ -543,85 +595,82 @@ static int partition_stage(shk_ctx *c, int src, uint64_t nmax, int *dst, const u
     // more (repeats: one k-mer a million times) raises SHK_E_SLOT_FULL and the level is redone the exact way; after two
     // such batches in a row the context stops trying.
     uint32_t cap = 0;
-    if (l + 1 == c->nlevels && l >= 1 && c->lv[l].out32 && !c->slots_off && !(l == 1 && hist1_ready)) {
+    if (l + 1 == c->nlevels && l >= 1 && c->lv[l].out32 && !b->slots_off && !(l == 1 && hist1_ready)) {
       uint64_t cp = 2 * c->cfg.max_batch_keys / (nb * P);
       if (cp > (1u << 20)) cp = 1u << 20;
       const double mean = (double)nmax / (double)(nb * P);
       if (cp >= 64 && (double)cp >= mean + 6.0 * sqrt(8.0 * mean + 1.0) + 16.0) cap = (uint32_t)cp;
     }
-    { ProfScope ps(c, KP_RP_PREP);
-      hipLaunchKernelGGL(k_rp_tile_first, dim3(nwin / 256 + 1), dim3(256), 0, c->stream, c->d_base[l], (uint32_t)nb, n_p, c->d_tfb); }
+    { ProfScope ps(c, b, KP_RP_PREP);
+      hipLaunchKernelGGL(k_rp_tile_first, dim3(nwin / 256 + 1), dim3(256), 0, b->stream, b->d_base[l], (uint32_t)nb, n_p, b->d_tfb); }
     for (;;) {
       ShkRpLevel lvl = c->lv[l];
 #ifdef SHK_DIAGNOSTICS   // timing ablations give INVALID results: compiled into diagnostic builds only (make DIAG=1)
       if (const char *e = getenv("SHK_RP_ABLATE")) lvl.ablate = (uint32_t)atoi(e);
 #endif
-      uint64_t *cursor = c->d_cursor;
+      uint64_t *cursor = b->d_cursor;
       if (cap) {
-        ProfScope ps(c, KP_RP_SLOTS);
-        cursor = c->d_base[l + 1];           // (ends up as the regions' end positions)
+        ProfScope ps(c, b, KP_RP_SLOTS);
+        cursor = b->d_base[l + 1];           // (ends up as the regions' end positions)
         lvl.slot_cap = cap;
-        hipLaunchKernelGGL(k_rp_slot_cursors, dim3((uint32_t)((nb * P) / 256 + 1 < 4096 ? (nb * P) / 256 + 1 : 4096)), dim3(256), 0, c->stream, cursor, nb * P, cap);
+        hipLaunchKernelGGL(k_rp_slot_cursors, dim3((uint32_t)((nb * P) / 256 + 1 < 4096 ? (nb * P) / 256 + 1 : 4096)), dim3(256), 0, b->stream, cursor, nb * P, cap);
       } else {
         const bool ready = (l == 0 && hist0_ready) || (l == 1 && hist1_ready);
         if (!ready && l == 0 && c->nlevels >= 2 && c->lv[0].bits + c->lv[1].bits <= 14 && c->lv[1].ng_log2 == 0 && !getenv("SHK_RP_HIST1")) {
           // the first pass over unsorted words counts the second level's digits as well (k_rp_hist2)
-          HIPCHK(hipMemsetAsync(c->d_hist[0], 0, (P << c->lv[0].ng_log2) * 8, c->stream));
-          HIPCHK(hipMemsetAsync(c->d_hist[1], 0, (P << c->lv[1].bits) * 8, c->stream));
-          ProfScope ps(c, KP_RP_HIST);
+          HIPCHK(hipMemsetAsync(b->d_hist[0], 0, (P << c->lv[0].ng_log2) * 8, b->stream));
+          HIPCHK(hipMemsetAsync(b->d_hist[1], 0, (P << c->lv[1].bits) * 8, b->stream));
+          ProfScope ps(c, b, KP_RP_HIST);
           const uint32_t wt = nwin / 1024 + 1;   // windows per workgroup (few workgroups: each flushes up to 2^14 counters)
           for (int si = 0; si < nsrc; si++)
-            hipLaunchKernelGGL((k_rp_hist2<14>), dim3(nwin / wt + 1), dim3(c->threads < 512 ? c->threads : 512), 0, c->stream, srcs[si].w, srcs[si].n_p,
-                               c->lv[0], c->lv[1], c->d_hist[0], c->d_hist[1], wt);
+            hipLaunchKernelGGL((k_rp_hist2<14>), dim3(nwin / wt + 1), dim3(c->threads < 512 ? c->threads : 512), 0, b->stream, srcs[si].w, srcs[si].n_p,
+                               c->lv[0], c->lv[1], b->d_hist[0], b->d_hist[1], wt);
           hist1_ready = true;
         } else if (!ready) {
-          HIPCHK(hipMemsetAsync(c->d_hist[l], 0, ((nb * P) << c->lv[l].ng_log2) * 8, c->stream));
-          ProfScope ps(c, KP_RP_HIST);
+          HIPCHK(hipMemsetAsync(b->d_hist[l], 0, ((nb * P) << c->lv[l].ng_log2) * 8, b->stream));
+          ProfScope ps(c, b, KP_RP_HIST);
           const uint32_t wt = nwin / 4096 + 1;   // windows per workgroup
           for (int si = 0; si < nsrc; si++)
-            hipLaunchKernelGGL(k_rp_hist, dim3(nwin / wt + 1), dim3(c->threads), 0, c->stream, srcs[si].w, srcs[si].n_p, srcs[si].base, c->d_tfb, c->lv[l],
-                               c->d_hist[l], wt);
+            hipLaunchKernelGGL(k_rp_hist, dim3(nwin / wt + 1), dim3(c->threads), 0, b->stream, srcs[si].w, srcs[si].n_p, srcs[si].base, b->d_tfb, c->lv[l],
+                               b->d_hist[l], wt);
         }
         if (c->lv[l].ng_log2) {
           // (first level only: nb = 1) sub-buckets in (digit, group) order; the next level's buckets are the digits
           const uint32_t ng = c->lv[l].ng_log2;
-          if (run_scan<uint64_t>(c, c->d_hist[l], P << ng, nullptr, c->d_base_sub)) return SHK_ERR_HIP;
-          HIPCHK(hipMemcpyAsync(c->d_cursor, c->d_base_sub, (P << ng) * 8, hipMemcpyDeviceToDevice, c->stream));
-          ProfScope ps(c, KP_RP_PREP);
-          hipLaunchKernelGGL(k_rp_group_bases, dim3((uint32_t)(P / 256 + 1)), dim3(256), 0, c->stream, c->d_base_sub, (uint32_t)P, ng, c->d_base[l + 1]);
+          if (run_scan<uint64_t>(c, b, b->d_hist[l], P << ng, nullptr, b->d_base_sub)) return SHK_ERR_HIP;
+          HIPCHK(hipMemcpyAsync(b->d_cursor, b->d_base_sub, (P << ng) * 8, hipMemcpyDeviceToDevice, b->stream));
+          ProfScope ps(c, b, KP_RP_PREP);
+          hipLaunchKernelGGL(k_rp_group_bases, dim3((uint32_t)(P / 256 + 1)), dim3(256), 0, b->stream, b->d_base_sub, (uint32_t)P, ng, b->d_base[l + 1]);
         } else {
-          if (run_scan<uint64_t>(c, c->d_hist[l], nb * P, nullptr, c->d_base[l + 1])) return SHK_ERR_HIP;
-          HIPCHK(hipMemcpyAsync(c->d_cursor, c->d_base[l + 1], nb * P * 8, hipMemcpyDeviceToDevice, c->stream));
+          if (run_scan<uint64_t>(c, b, b->d_hist[l], nb * P, nullptr, b->d_base[l + 1])) return SHK_ERR_HIP;
+          HIPCHK(hipMemcpyAsync(b->d_cursor, b->d_base[l + 1], nb * P * 8, hipMemcpyDeviceToDevice, b->stream));
         }
       }
-      { ProfScope ps(c, KP_RP_SCATTER);
+      { ProfScope ps(c, b, KP_RP_SCATTER);
         for (int si = 0; si < nsrc; si++) {
           const Src &S = srcs[si];
           if (l == 0 && c->lv[0].ng_log2)      // (window groups are defined on the first level's 16384-key windows: SHK_RP_TILE0_LOG2)
-            hipLaunchKernelGGL((k_rp_scatter<SHK_RP_TILE0_LOG2, 1024>), dim3((uint32_t)(S.n >> SHK_RP_TILE0_LOG2) + 1), dim3(1024), 0, c->stream, S.w,
-                               c->d_words[cur ^ 1], S.n_p, S.base, c->d_tfb, lvl, cursor, c->d_err);
+            hipLaunchKernelGGL((k_rp_scatter<SHK_RP_TILE0_LOG2, 1024>), dim3((uint32_t)(S.n >> SHK_RP_TILE0_LOG2) + 1), dim3(1024), 0, b->stream, S.w,
+                               b->d_words[cur ^ 1], S.n_p, S.base, b->d_tfb, lvl, cursor, b->d_err);
           else if (c->threads >= 512 && l + 1 < c->nlevels && c->lv[l].bits <= 8 && !getenv("SHK_RP_NARROW"))
             // a level in the middle: 16384-key windows as at the first level (digit runs of 1 KB instead of 256 bytes:
             // 2.85 -> 2.25 ms per 832 M keys). Not the last level: its 4-byte records in slots gain nothing (3.4 ms either way)
-            hipLaunchKernelGGL((k_rp_scatter<SHK_RP_TILE0_LOG2, 1024, 256>), dim3((uint32_t)(S.n >> SHK_RP_TILE0_LOG2) + 1), dim3(1024), 0, c->stream, S.w,
-                               c->d_words[cur ^ 1], S.n_p, S.base, c->d_tfb, lvl, cursor, c->d_err);
+            hipLaunchKernelGGL((k_rp_scatter<SHK_RP_TILE0_LOG2, 1024, 256>), dim3((uint32_t)(S.n >> SHK_RP_TILE0_LOG2) + 1), dim3(1024), 0, b->stream, S.w,
+                               b->d_words[cur ^ 1], S.n_p, S.base, b->d_tfb, lvl, cursor, b->d_err);
           else
-            hipLaunchKernelGGL((k_rp_scatter<12, SHK_RP_THREADS>), dim3((uint32_t)(S.n / SHK_RP_TILE + 1)), dim3(SHK_RP_THREADS), 0, c->stream, S.w,
-                               c->d_words[cur ^ 1], S.n_p, S.base, c->d_tfb, lvl, cursor, c->d_err);
+            hipLaunchKernelGGL((k_rp_scatter<12, SHK_RP_THREADS>), dim3((uint32_t)(S.n / SHK_RP_TILE + 1)), dim3(SHK_RP_THREADS), 0, b->stream, S.w,
+                               b->d_words[cur ^ 1], S.n_p, S.base, b->d_tfb, lvl, cursor, b->d_err);
         } }
       if (!cap) break;
       uint32_t bits = 0;
-      if (fetch_err(c, &bits)) return SHK_ERR_HIP;
+      if (fetch_err(b, &bits)) return SHK_ERR_HIP;
       if (bits & ~SHK_E_SLOT_FULL) return map_err_bits(bits & ~SHK_E_SLOT_FULL);
-      if (!bits) { c->region_cap = cap; c->slot_overflows = 0; break; }
-      if (++c->slot_overflows >= 2) c->slots_off = 1;
+      if (!bits) { b->region_cap = cap; b->slot_overflows = 0; break; }
+      if (++b->slot_overflows >= 2) b->slots_off = 1;
       cap = 0;                               // a region overflowed its slot: the same level again with exact bases
     }
     cur ^= 1;
-    in = c->d_words[cur];
-  }
-  if (c->nlevels == 0) {
-    // a single region: its keys are [0, n)
+    in = b->d_words[cur];
   }
   HIPCHK(hipGetLastError());
   *dst = cur;
@@ -1221,6 +1270,28 @@ static int finish(shk_ctx *c, int rc) {
   return map_err_bits(bits);
 }
 
+// The front end of one batch: text + chunk table -> key words partitioned by region in b->d_words[*dst], *nwords of them;
+// the regions' offsets are in b->d_base[nlevels] and lie as *region_cap says (ShkStageBufs::region_cap). Errors the
+// partition's kernels raise are left in b->d_err for the caller's next fetch_err.
+static int front_end(const shk_ctx *c, ShkStageBufs *b, const void *text, int on_device, uint64_t text_bytes, const uint64_t *chunk_off,
+                     const uint64_t *chunk_len, uint32_t nchunks, uint64_t *nwords, int *dst, uint32_t *region_cap) {
+  const bool roll = roll_path(c);
+  bool h1 = false;
+  int rc = roll ? roll_stage(c, b, text, on_device, text_bytes, chunk_off, chunk_len, nchunks, 0, 1, &h1)
+                : hash_stage(c, b, text, on_device, text_bytes, chunk_off, chunk_len, nchunks, 0, 1, true);
+  if (rc) return rc;
+  uint32_t bits = 0;
+  HIPCHK(hipMemcpyAsync(b->h_pinned + 42, b->d_scalars + 1, 8, hipMemcpyDeviceToHost, b->stream));
+  if (fetch_err(b, &bits)) return SHK_ERR_HIP;
+  if (bits) return map_err_bits(bits);
+  *nwords = b->h_pinned[42];
+  if (*nwords > c->cfg.max_batch_keys) return SHK_ERR_BATCH;
+  // (the roll kernels leave the words partitioned by the first digit; the hash kernel has counted the first level's digits)
+  rc = roll ? partition_stage(c, b, 0, *nwords, dst, nullptr, false, 1, h1) : partition_stage(c, b, 0, *nwords, dst, nullptr, true);
+  *region_cap = b->region_cap;
+  return rc;
+}
+
 extern "C" int shk_count_chunks(shk_ctx *c, const void *text, int text_on_device, uint64_t text_bytes,
                                 const uint64_t *chunk_off, const uint64_t *chunk_len, uint32_t nchunks,
                                 shk_batch_stats *stats) {
@@ -1228,20 +1299,12 @@ extern "C" int shk_count_chunks(shk_ctx *c, const void *text, int text_on_device
   shk_batch_stats st;
   memset(&st, 0, sizeof(st));
   HIPCHK(hipSetDevice(c->dev));
-  const bool roll = roll_path(c);
-  bool h1 = false;
-  int rc = roll ? roll_stage(c, text, text_on_device, text_bytes, chunk_off, chunk_len, nchunks, 0, 1, &h1)
-                : hash_stage(c, text, text_on_device, text_bytes, chunk_off, chunk_len, nchunks, 0, 1, true);
-  if (rc) return finish(c, rc);
-  uint32_t bits = 0;
-  HIPCHK(hipMemcpyAsync(c->h_pinned + 42, c->d_scalars + 1, 8, hipMemcpyDeviceToHost, c->stream));
-  if (fetch_err(c, &bits)) return SHK_ERR_HIP;
-  if (bits) { prof_collect(c); return map_err_bits(bits); }
-  const uint64_t nwords = c->h_pinned[42];
-  if (nwords > c->cfg.max_batch_keys) { prof_collect(c); return SHK_ERR_BATCH; }
+  if (upload_wait(c, text, text_on_device, c->stream)) return SHK_ERR_HIP;
+  uint64_t nwords = 0;
   int dst = 0;
-  // (the roll kernels leave the words partitioned by the first digit; the hash kernel has counted the first level's digits)
-  rc = roll ? partition_stage(c, 0, nwords, &dst, nullptr, false, 1, h1) : partition_stage(c, 0, nwords, &dst, nullptr, true);
+  uint32_t cap = 0;
+  // (the error word behind the partition is finish()'s, after the rebuild: no synchronisation in between)
+  int rc = front_end(c, c, text, text_on_device, text_bytes, chunk_off, chunk_len, nchunks, &nwords, &dst, &cap);
   if (rc) return finish(c, rc);
   rc = merge_stage(c, c->d_words[dst], nchunks, nwords, &st);
   if (stats) *stats = st;
@@ -1253,139 +1316,70 @@ extern "C" int shk_count_chunks(shk_ctx *c, const void *text, int text_on_device
 // the CUs' LDS pipelines and instruction issue), one after the other on one stream. The two halves of DIFFERENT batches
 // have nothing to do with each other until the rebuild reads the partitioned words, so the front end of batch s+1 can
 // run on a second stream while batch s is rebuilt: shk_prepare_chunks starts it and returns, shk_count_prepared takes
-// the oldest prepared batch through the rebuild. Two batches may be prepared ahead. The front end works in a shadow of the
-// context: its own stream, scalars, error word, scan scratch and partition buffers; two slots of (partitioned words,
-// region bases) alternate between "being prepared" and "being rebuilt". The shadow runs the unchanged stage functions
-// (host synchronisations included) in a helper thread, so the caller's thread is free to drive the rebuild.
+// the oldest prepared batch through the rebuild. Two batches may be prepared ahead. The overlapped front end has a
+// ShkStageBufs of its own (a non-blocking stream, scalars, error word, scan scratch, partition buffers, kernel times) and
+// reads the context for geometry and configuration only; two slots of (partitioned words, region bases) alternate
+// between "being prepared" and "being rebuilt". It runs the same front_end as the serial path (host synchronisations
+// included) in a helper thread, so the caller's thread is free to drive the rebuild.
 struct ShkFrontSlot {
   uint64_t *words = nullptr;    // the buffer the last partition level writes into (and the roll kernels, two levels earlier)
   uint64_t *base = nullptr;     // region bases of that batch (region ENDS when cap != 0)
-  uint32_t cap = 0;             // shk_ctx::region_cap of that batch
+  uint32_t cap = 0;             // ShkStageBufs::region_cap of that batch
   std::thread th;
   bool busy = false;
-  int rc = 0, dst = 0;
+  int rc = 0;
   uint64_t nwords = 0;
   uint32_t nchunks = 0;
 };
 struct ShkFront {
-  shk_ctx *f = nullptr;
+  ShkStageBufs b;               // (lent: d_words[] are a slot's words and scratch, d_base[nlevels] the slot's base)
   ShkFrontSlot slot[2];
   int head = 0, count = 0;      // oldest prepared slot, prepared slots
   int par = 0;                  // index of d_words[] the last level writes into
-  uint64_t *scratch = nullptr;  // the other d_words[] of the shadow
+  uint64_t *scratch = nullptr;  // the other d_words[] of every batch
 };
 
 static int front_init(shk_ctx *c) {
   ShkFront *F = new ShkFront();
-  shk_ctx *f = new shk_ctx(*c);
-  F->f = f;
-  f->front = nullptr;
-  f->pending.clear(); f->evpool.clear();
-  f->copy_stream = hipStream_t(); f->d_up[0] = f->d_up[1] = nullptr; f->up_pending[0] = f->up_pending[1] = 0;
-  for (int i = 0; i < KP_N; i++) { f->prof_ms[i] = 0; f->prof_n[i] = 0; }
   c->front = F;
-  const uint32_t maxch = SHK_MAX_CHUNKS;
-  const uint64_t capk = c->cfg.max_batch_keys;
-  // everything the front end writes is the shadow's own (null first: a failed allocation leaves nothing dangling)
-  f->d_text = nullptr; f->d_chunk_off = f->d_chunk_len = f->d_nlines = f->d_reads_base = f->d_rd_start = f->d_rd_end = nullptr;
-  f->d_rd_chunk = nullptr; f->d_nkeys = nullptr; f->d_key_base = nullptr; f->d_scalars = nullptr; f->d_block_sums = nullptr;
-  f->d_base_sub = nullptr; f->d_cursor = nullptr; f->d_tfb = nullptr; f->d_err = nullptr; f->h_pinned = nullptr;
-  for (int l = 0; l < 4; l++) f->d_hist[l] = nullptr;
-  for (int l = 0; l < 5; l++) f->d_base[l] = nullptr;
-  f->d_words[0] = f->d_words[1] = nullptr;
-  // (a higher stream priority changes nothing measurable: the rebuild's small workgroups refill every CU as fast as they
-  // leave it, whatever the priority of the queue whose big workgroups are waiting)
-  HIPCHK(hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking));
-  if (dmalloc(&f->d_text, c->cfg.max_batch_bytes + 64)) return SHK_ERR_HIP;
-  if (dmalloc(&f->d_chunk_off, maxch) || dmalloc(&f->d_chunk_len, maxch) || dmalloc(&f->d_nlines, (uint64_t)maxch * SHK_PARSE_SEGS) ||
-      dmalloc(&f->d_reads_base, maxch + 1)) return SHK_ERR_HIP;
-  if (dmalloc(&f->d_rd_start, c->max_reads + 1) || dmalloc(&f->d_rd_end, c->max_reads + 1) || dmalloc(&f->d_nkeys, c->max_reads + 1) ||
-      dmalloc(&f->d_rd_chunk, c->max_reads + 1) || dmalloc(&f->d_key_base, c->max_reads + 2)) return SHK_ERR_HIP;
-  if (dmalloc(&f->d_scalars, 64)) return SHK_ERR_HIP;
-  HIPCHK(hipMemsetAsync(f->d_scalars, 0, 64 * 8, f->stream));
-  { uint64_t mx = capk > c->max_reads ? capk : c->max_reads;
-    uint64_t pw = 1ULL << c->rbits;
-    if (pw > mx) mx = pw;
-    if (dmalloc(&f->d_block_sums, mx / SHK_SCAN_TILE + 4 + 8192)) return SHK_ERR_HIP; }
-  { uint64_t nb = 1;
-    if (dmalloc(&f->d_base[0], 2)) return SHK_ERR_HIP;
-    for (uint32_t l = 0; l < c->nlevels; l++) {
-      const uint64_t n = nb << c->lv[l].bits;
-      if (dmalloc(&f->d_hist[l], (n << c->lv[l].ng_log2) + 1)) return SHK_ERR_HIP;
-      if (l + 1 < c->nlevels && dmalloc(&f->d_base[l + 1], n + 2)) return SHK_ERR_HIP;
-      if (l + 1 == c->nlevels) for (int k2 = 0; k2 < 2; k2++) if (dmalloc(&F->slot[k2].base, n + 2)) return SHK_ERR_HIP;
-      if (l == 0 && dmalloc(&f->d_base_sub, (n << c->lv[0].ng_log2) + 2)) return SHK_ERR_HIP;
-      nb = n;
-    }
-    { const uint64_t first = (1ULL << (c->lv[0].bits + c->lv[0].ng_log2));
-      if (dmalloc(&f->d_cursor, (nb > first ? nb : first) + 2)) return SHK_ERR_HIP; } }
-  if (dmalloc(&f->d_tfb, capk / SHK_RP_TILE + 2)) return SHK_ERR_HIP;
-  if (dmalloc(&f->d_err, 4)) return SHK_ERR_HIP;
-  HIPCHK(hipMemsetAsync(f->d_err, 0, 16, f->stream));
-  HIPCHK(hipHostMalloc((void **)&f->h_pinned, 64 * sizeof(uint64_t), hipHostMallocDefault));
+  { int rc = bufs_alloc(c, &F->b, true); if (rc) return rc; }
   // the roll kernels write d_words[0]; every further level flips: the last one lands in d_words[(nlevels - 1) & 1]
   F->par = roll_path(c) ? (int)((c->nlevels - 1) & 1) : (int)(c->nlevels & 1);
-  if (dmalloc(&F->scratch, capk + 1) || dmalloc(&F->slot[0].words, capk + 1) || dmalloc(&F->slot[1].words, capk + 1)) return SHK_ERR_HIP;
-  HIPCHK(hipStreamSynchronize(f->stream));
+  const uint64_t capk = c->cfg.max_batch_keys;
+  if (dmalloc(&F->scratch, capk + 1)) return SHK_ERR_HIP;
+  for (int k2 = 0; k2 < 2; k2++)
+    if (dmalloc(&F->slot[k2].words, capk + 1) || dmalloc(&F->slot[k2].base, level_out(c, c->nlevels - 1) + 2)) return SHK_ERR_HIP;
   return SHK_OK;
 }
 static void front_destroy(shk_ctx *c) {
   ShkFront *F = c->front;
   if (!F) return;
   for (int k2 = 0; k2 < 2; k2++) if (F->slot[k2].th.joinable()) F->slot[k2].th.join();
-  shk_ctx *f = F->f;
-  if (f) {
-    if (f->stream) hipStreamSynchronize(f->stream);
-    prof_collect(f);
-    for (size_t i = 0; i < f->evpool.size(); i++) hipEventDestroy(f->evpool[i]);
-    hipFree(f->d_text); hipFree(f->d_chunk_off); hipFree(f->d_chunk_len); hipFree(f->d_nlines); hipFree(f->d_reads_base);
-    hipFree(f->d_rd_start); hipFree(f->d_rd_end); hipFree(f->d_rd_chunk); hipFree(f->d_nkeys); hipFree(f->d_key_base); hipFree(f->d_scalars);
-    hipFree(f->d_block_sums); hipFree(f->d_base[0]); hipFree(f->d_base_sub);
-    for (uint32_t l = 0; l < c->nlevels; l++) { hipFree(f->d_hist[l]); if (l + 1 < c->nlevels) hipFree(f->d_base[l + 1]); }
-    hipFree(f->d_cursor); hipFree(f->d_tfb); hipFree(f->d_err);
-    if (f->h_pinned) hipHostFree(f->h_pinned);
-    if (f->stream) hipStreamDestroy(f->stream);
-    delete f;
-  }
+  bufs_free(c, &F->b);
   hipFree(F->scratch);
   for (int k2 = 0; k2 < 2; k2++) { hipFree(F->slot[k2].words); hipFree(F->slot[k2].base); }
   delete F;
   c->front = nullptr;
 }
 
-// the front end of one batch in the shadow context; runs in the helper thread
-static void front_run(shk_ctx *c, ShkFrontSlot *S, const void *text, int on_device, uint64_t text_bytes, std::vector<uint64_t> off,
+// the front end of one batch in the front's own buffers; runs in the helper thread
+static void front_run(const shk_ctx *c, ShkFrontSlot *S, const void *text, int on_device, uint64_t text_bytes, std::vector<uint64_t> off,
                       std::vector<uint64_t> len) {
   ShkFront *F = c->front;
-  shk_ctx *f = F->f;
+  ShkStageBufs *b = &F->b;
   hipSetDevice(c->dev);
-  f->prof_on = c->prof_on;
-  f->d_words[F->par] = S->words; f->d_words[F->par ^ 1] = F->scratch;
-  f->d_base[c->nlevels] = S->base;
-  const uint32_t nchunks = (uint32_t)off.size();
-  const bool roll = roll_path(c);
-  S->nwords = 0; S->nchunks = nchunks;
-  bool h1 = false;
-  int rc = roll ? roll_stage(f, text, on_device, text_bytes, off.data(), len.data(), nchunks, 0, 1, &h1)
-                : hash_stage(f, text, on_device, text_bytes, off.data(), len.data(), nchunks, 0, 1, true);
-  uint32_t bits = 0;
+  b->d_words[F->par] = S->words; b->d_words[F->par ^ 1] = F->scratch;
+  b->d_base[c->nlevels] = S->base;
+  S->nwords = 0; S->nchunks = (uint32_t)off.size();
+  int dst = 0;
+  int rc = front_end(c, b, text, on_device, text_bytes, off.data(), len.data(), S->nchunks, &S->nwords, &dst, &S->cap);
   if (!rc) {
-    if (hipMemcpyAsync(f->h_pinned + 42, f->d_scalars + 1, 8, hipMemcpyDeviceToHost, f->stream) != hipSuccess || fetch_err(f, &bits)) rc = SHK_ERR_HIP;
+    uint32_t bits = 0;
+    if (fetch_err(b, &bits)) rc = SHK_ERR_HIP;            // (synchronises the front's stream: the batch is ready)
     else if (bits) rc = map_err_bits(bits);
-    else if (f->h_pinned[42] > c->cfg.max_batch_keys) rc = SHK_ERR_BATCH;
+    else if (dst != F->par) rc = SHK_ERR_CORRUPT;         // (the slot's buffer must be the one the last level wrote)
   }
-  if (!rc) {
-    S->nwords = f->h_pinned[42];
-    int dst = 0;
-    rc = roll ? partition_stage(f, 0, S->nwords, &dst, nullptr, false, 1, h1) : partition_stage(f, 0, S->nwords, &dst, nullptr, true);
-    S->dst = dst; S->cap = f->region_cap;
-    if (!rc) {
-      if (fetch_err(f, &bits)) rc = SHK_ERR_HIP;          // (synchronises the shadow's stream: the batch is ready)
-      else if (bits) rc = map_err_bits(bits);
-      else if (dst != F->par) rc = SHK_ERR_CORRUPT;       // (the slot's buffer must be the one the last level wrote)
-    }
-  }
-  if (rc) hipStreamSynchronize(f->stream);
+  if (rc) hipStreamSynchronize(b->stream);
   S->rc = rc;
 }
 
@@ -1398,12 +1392,10 @@ extern "C" int shk_prepare_chunks(shk_ctx *c, const void *text, int text_on_devi
   ShkFront *F = c->front;
   if (F->count == 2) return SHK_ERR_BATCH;                // two batches are prepared already: count one first
   ShkFrontSlot *S = &F->slot[(F->head + F->count) & 1];
-  // one front end at a time: the previous one (the other slot's) must have left the shadow's buffers
+  // one front end at a time: the previous one (the other slot's) must have left the front's buffers
   ShkFrontSlot *O = &F->slot[(F->head + F->count + 1) & 1];
   if (O->th.joinable()) O->th.join();
-  if (text_on_device)
-    for (int b = 0; b < 2; b++)   // a buffer of shk_upload_text whose copy may still be running
-      if (c->d_up[b] && text == (const void *)c->d_up[b] && c->up_pending[b]) { HIPCHK(hipStreamWaitEvent(F->f->stream, c->up_done[b], 0)); c->up_pending[b] = 0; }
+  if (upload_wait(c, text, text_on_device, F->b.stream)) return SHK_ERR_HIP;
   std::vector<uint64_t> off(chunk_off, chunk_off + nchunks), len(chunk_len, chunk_len + nchunks);
   S->busy = true;
   F->count++;
@@ -1435,13 +1427,13 @@ extern "C" int shk_count_prepared(shk_ctx *c, shk_batch_stats *stats) {
   if (S->th.joinable()) S->th.join();
   F->head ^= 1; F->count--;
   S->busy = false;
-  shk_ctx *f = F->f;
+  ShkStageBufs *f = &F->b;
   shk_batch_stats st;
   memset(&st, 0, sizeof(st));
   if (stats) *stats = st;
-  // the front end's kernel times join the context's (its events were recorded on the shadow's stream)
+  // the front end's kernel times join the context's (its events were recorded on the front's stream)
   { // (the other slot's front end may be running: it only appends to f->pending from its own thread, so collect
-    // what THIS batch left only when nobody else is inside the shadow)
+    // what THIS batch left only when nobody else is inside the front's buffers)
     ShkFrontSlot *O = &F->slot[F->head];
     if (!(O->busy && O->th.joinable())) {
       prof_collect(f);
@@ -1490,13 +1482,24 @@ extern "C" int shk_hash_chunks(shk_ctx *c, const void *text, int text_on_device,
                                uint64_t **d_words, uint64_t *nwords) {
   if (!c || !text || !d_words || !nwords) return SHK_ERR_ARG;
   HIPCHK(hipSetDevice(c->dev));
-  int rc = hash_stage(c, text, text_on_device, text_bytes, chunk_off, chunk_len, nchunks, c->cfg.shard_index, c->cfg.num_shards ? c->cfg.num_shards : 1);
+  if (upload_wait(c, text, text_on_device, c->stream)) return SHK_ERR_HIP;
+  int rc = hash_stage(c, c, text, text_on_device, text_bytes, chunk_off, chunk_len, nchunks, c->cfg.shard_index, c->cfg.num_shards ? c->cfg.num_shards : 1);
   if (rc) return finish(c, rc);
   HIPCHK(hipMemcpyAsync(c->h_pinned + 42, c->d_scalars + 1, 8, hipMemcpyDeviceToHost, c->stream));
   rc = finish(c, 0);
   *d_words = c->d_words[0];
   *nwords = c->h_pinned[42];
   return rc;
+}
+
+// External words -> partitioned by region in d_words[*dst]: their number goes to d_scalars[1], and the first partition
+// level reads the caller's buffer in place (no staging copy), be it one of the context's own or not.
+static int partition_words(shk_ctx *c, const uint64_t *d_words, uint64_t nwords, int *dst) {
+  c->h_pinned[43] = nwords;
+  HIPCHK(hipMemcpyAsync(c->d_scalars + 1, c->h_pinned + 43, 8, hipMemcpyHostToDevice, c->stream));
+  return d_words == c->d_words[0] ? partition_stage(c, c, 0, nwords, dst)
+       : d_words == c->d_words[1] ? partition_stage(c, c, 1, nwords, dst)
+                                  : partition_stage(c, c, 0, nwords, dst, d_words);
 }
 
 extern "C" int shk_count_words(shk_ctx *c, const uint64_t *d_words, uint64_t nwords, uint32_t nchunks,
@@ -1506,17 +1509,24 @@ extern "C" int shk_count_words(shk_ctx *c, const uint64_t *d_words, uint64_t nwo
   shk_batch_stats st;
   memset(&st, 0, sizeof(st));
   HIPCHK(hipSetDevice(c->dev));
-  c->h_pinned[43] = nwords;
-  HIPCHK(hipMemcpyAsync(c->d_scalars + 1, c->h_pinned + 43, 8, hipMemcpyHostToDevice, c->stream));
   int dst = 0;
-  // the first partition level reads the caller's buffer in place (no staging copy)
-  int rc = d_words == c->d_words[0] ? partition_stage(c, 0, nwords, &dst)
-         : d_words == c->d_words[1] ? partition_stage(c, 1, nwords, &dst)
-                                    : partition_stage(c, 0, nwords, &dst, d_words);
+  int rc = partition_words(c, d_words, nwords, &dst);
   if (rc) return finish(c, rc);
   rc = merge_stage(c, c->d_words[dst], nchunks, nwords, &st);
   if (stats) *stats = st;
   return finish(c, rc);
+}
+
+// where routed words go: one of two alternating send buffers (allocated on first use), or d_words[1] when
+// SHK_ROUTE_SINGLE_BUFFER is set
+static int send_buffer(shk_ctx *c, uint64_t **send) {
+  *send = c->d_words[1];
+  if (getenv("SHK_ROUTE_SINGLE_BUFFER")) return SHK_OK;
+  const int b = c->send_next;
+  if (!c->d_send[b] && dmalloc(&c->d_send[b], c->cfg.max_batch_keys + 1)) return SHK_ERR_HIP;
+  *send = c->d_send[b];
+  c->send_next ^= 1;
+  return SHK_OK;
 }
 
 extern "C" int shk_route_words(shk_ctx *c, uint64_t nwords, uint32_t nshards, uint64_t **d_out, uint64_t *counts) {
@@ -1525,13 +1535,8 @@ extern "C" int shk_route_words(shk_ctx *c, uint64_t nwords, uint32_t nshards, ui
   HIPCHK(hipSetDevice(c->dev));
   uint32_t lg = 0;
   while ((1u << lg) < nshards) lg++;
-  uint64_t *send = c->d_words[1];
-  if (!getenv("SHK_ROUTE_SINGLE_BUFFER")) {
-    const int b = c->send_next;
-    if (!c->d_send[b] && dmalloc(&c->d_send[b], c->cfg.max_batch_keys + 1)) return SHK_ERR_HIP;
-    send = c->d_send[b];
-    c->send_next ^= 1;
-  }
+  uint64_t *send;
+  if (send_buffer(c, &send)) return SHK_ERR_HIP;
   if (lg == 0) {
     HIPCHK(hipMemcpyAsync(send, c->d_words[0], nwords * 8, hipMemcpyDeviceToDevice, c->stream));
     *d_out = send; counts[0] = nwords;
@@ -1547,7 +1552,6 @@ extern "C" int shk_route_words(shk_ctx *c, uint64_t nwords, uint32_t nshards, ui
   const uint64_t *n_p = c->d_scalars + 1;
   const uint32_t nwin = (uint32_t)(nwords / SHK_RP_TILE + 1);
   uint64_t *hist = c->d_block_sums;            // scratch: nshards <= 1024 words each
-  uint64_t *base = c->d_block_sums + 2048;
   uint64_t *cursor = c->d_block_sums + 4096;
   { ProfScope ps(c, KP_RP_PREP);
     hipLaunchKernelGGL(k_rp_base1, dim3(1), dim3(64), 0, c->stream, n_p, c->d_base[0]);
@@ -1556,14 +1560,12 @@ extern "C" int shk_route_words(shk_ctx *c, uint64_t nwords, uint32_t nshards, ui
   { ProfScope ps(c, KP_RP_HIST);
     const uint32_t wt = nwin / 4096 + 1;
     hipLaunchKernelGGL(k_rp_hist, dim3(nwin / wt + 1), dim3(c->threads), 0, c->stream, c->d_words[0], n_p, c->d_base[0], c->d_tfb, lv, hist, wt); }
-  HIPCHK(hipMemcpyAsync(c->h_pinned + 16, hist, nshards * 8 > 16 * 8 ? 16 * 8 : nshards * 8, hipMemcpyDeviceToHost, c->stream));
   std::vector<uint64_t> hh(nshards);
   HIPCHK(hipMemcpyAsync(hh.data(), hist, nshards * 8, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   std::vector<uint64_t> bb(nshards + 1, 0);
   for (uint32_t i = 0; i < nshards; i++) { counts[i] = hh[i]; bb[i + 1] = bb[i] + hh[i]; }
   HIPCHK(hipMemcpyAsync(cursor, bb.data(), nshards * 8, hipMemcpyHostToDevice, c->stream));
-  (void)base;
   { ProfScope ps(c, KP_RP_SCATTER);
     hipLaunchKernelGGL((k_rp_scatter<12, SHK_RP_THREADS>), dim3(nwin), dim3(SHK_RP_THREADS), 0, c->stream, c->d_words[0], send, n_p,
                        c->d_base[0], c->d_tfb, lv, cursor, c->d_err); }
@@ -1586,17 +1588,13 @@ extern "C" int shk_hash_route_chunks(shk_ctx *c, const void *text, int text_on_d
   while ((1u << lg) < nshards) lg++;
   if (c->cfg.qb < SHK_REGION_LOG2 + lg) return SHK_ERR_ARG;
   const uint32_t chunk_first = c->cfg.shard_index, chunk_mul = c->cfg.num_shards ? c->cfg.num_shards : 1;
-  if (nchunks == 0 || nchunks > SHK_MAX_CHUNKS || chunk_first + (uint64_t)(nchunks - 1) * chunk_mul >= SHK_MAX_CHUNKS) return SHK_ERR_BATCH;
-  uint64_t *send = c->d_words[1];
-  if (!getenv("SHK_ROUTE_SINGLE_BUFFER")) {
-    const int b = c->send_next;
-    if (!c->d_send[b] && dmalloc(&c->d_send[b], c->cfg.max_batch_keys + 1)) return SHK_ERR_HIP;
-    send = c->d_send[b];
-    c->send_next ^= 1;
-  }
+  if (!chunk_labels_ok(nchunks, chunk_first, chunk_mul)) return SHK_ERR_BATCH;
+  uint64_t *send;
+  if (send_buffer(c, &send)) return SHK_ERR_HIP;
   const uint8_t *dtext;
   uint64_t nreads;
-  int rc = parse_stage(c, text, text_on_device, text_bytes, chunk_off, chunk_len, nchunks, &dtext, &nreads);
+  if (upload_wait(c, text, text_on_device, c->stream)) return SHK_ERR_HIP;
+  int rc = parse_stage(c, c, text, text_on_device, text_bytes, chunk_off, chunk_len, nchunks, &dtext, &nreads);
   if (rc) return finish(c, rc);
   // The words are binned by MORE bits than the owner's (7, when the filter has them): with a handful of bins every
   // lane's LDS atomic lands on the same few counters (one rank: 64-way serialised, the kernels took 3.3 and 8.3 ms
@@ -1607,24 +1605,16 @@ extern "C" int shk_hash_route_chunks(shk_ctx *c, const void *text, int text_on_d
   uint64_t *hist = c->d_block_sums;            // scratch: nbins <= 1024 words each
   uint64_t *cursor = c->d_block_sums + 4096;
   ShkRollArgs A;
-  A.text = dtext; A.safe_end = (text_bytes + 15) & ~15ULL;
-  A.rd_start = c->d_rd_start; A.rd_end = c->d_rd_end; A.nreads_p = c->d_scalars + 0; A.rd_chunk = c->d_rd_chunk;
-  A.chunk_first = chunk_first; A.chunk_mul = chunk_mul; A.k = c->cfg.k; A.hb = c->cfg.hb;
+  roll_args(c, c, A, dtext, text_bytes, chunk_first, chunk_mul);
   A.q_lo = 0;                                   // (owners are ranges of the WHOLE filter's quotients)
   A.dig_shift = rb - db; A.dig_bits = db;
   A.hist_shift = A.dig_shift; A.hist_bits = db;
-  A.hist = hist; A.cursor = cursor; A.out = send; A.cap = c->cfg.max_batch_keys; A.err = c->d_err;
-  rc = pack_stage(c, A, nreads, text_bytes, c->d_words[0]);      // (d_words[0]: filled by shk_stage_words, after this call)
+  A.hist = hist; A.cursor = cursor; A.out = send;
+  rc = pack_stage(c, c, A, nreads, text_bytes, c->d_words[0]);      // (d_words[0]: filled by shk_stage_words, after this call)
   if (rc) return finish(c, rc);
   HIPCHK(hipMemsetAsync(hist, 0, nbins * 8, c->stream));     // (behind pack_stage, whose scan uses the head of d_block_sums too)
   { ProfScope ps(c, KP_ROLL_HIST);
-    if (c->threads >= 512) {
-      const uint64_t blocks = nreads / 256 + 1;
-      hipLaunchKernelGGL((k_roll_hist<10, 256>), dim3((uint32_t)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, c->stream, A);
-    } else {
-      const uint64_t blocks = nreads / 64 + 1;
-      hipLaunchKernelGGL((k_roll_hist<10, 64>), dim3((uint32_t)(blocks < 64 ? blocks : 64)), dim3(64), 0, c->stream, A);
-    } }
+    launch_roll_hist(c, c, A, nreads, false); }
   std::vector<uint64_t> hh(nbins);
   HIPCHK(hipMemcpyAsync(hh.data(), hist, nbins * 8, hipMemcpyDeviceToHost, c->stream));
   uint32_t bits = 0;
@@ -1636,14 +1626,7 @@ extern "C" int shk_hash_route_chunks(shk_ctx *c, const void *text, int text_on_d
   *nwords = bb[nbins];
   if (bb[nbins] > c->cfg.max_batch_keys) { prof_collect(c); return SHK_ERR_BATCH; }
   HIPCHK(hipMemcpyAsync(cursor, bb.data(), nbins * 8, hipMemcpyHostToDevice, c->stream));
-  { ProfScope ps(c, KP_ROLL_SCATTER);
-    if (c->threads >= 512) {
-      const uint64_t blocks = nreads / 1024 + 1;
-      hipLaunchKernelGGL((k_roll_scatter<1024, 1>), dim3((uint32_t)(blocks < 512 ? blocks : 512)), dim3(1024), 0, c->stream, A);
-    } else {
-      const uint64_t blocks = nreads / 64 + 1;
-      hipLaunchKernelGGL((k_roll_scatter<64, 4>), dim3((uint32_t)(blocks < 64 ? blocks : 64)), dim3(64), 0, c->stream, A);
-    } }
+  launch_roll_scatter(c, c, A, nreads);
   HIPCHK(hipGetLastError());
   *d_out = send;
   return finish(c, 0);
@@ -1675,7 +1658,7 @@ extern "C" int shk_stage_words_pair(shk_ctx *c, const uint64_t *d_a, uint64_t na
   HIPCHK(hipMemcpyAsync(c->d_scalars + 40, c->h_pinned + 56, 48, hipMemcpyHostToDevice, c->stream));
   c->stage2_b = d_b; c->stage2_na = na; c->stage2_nb = nb;
   int dst = 0;
-  int rc = partition_stage(c, 0, na + nb, &dst, d_a);
+  int rc = partition_stage(c, c, 0, na + nb, &dst, d_a);
   c->stage2_b = nullptr;
   c->staged = dst;
   return finish(c, rc);
@@ -1685,13 +1668,8 @@ extern "C" int shk_stage_words(shk_ctx *c, const uint64_t *d_words, uint64_t nwo
   if (!c || (!d_words && nwords)) return SHK_ERR_ARG;
   if (nwords > c->cfg.max_batch_keys) return SHK_ERR_BATCH;
   HIPCHK(hipSetDevice(c->dev));
-  c->h_pinned[43] = nwords;
-  HIPCHK(hipMemcpyAsync(c->d_scalars + 1, c->h_pinned + 43, 8, hipMemcpyHostToDevice, c->stream));
   int dst = 0;
-  // the first partition level reads the caller's buffer in place (no staging copy)
-  int rc = d_words == c->d_words[0] ? partition_stage(c, 0, nwords, &dst)
-         : d_words == c->d_words[1] ? partition_stage(c, 1, nwords, &dst)
-                                    : partition_stage(c, 0, nwords, &dst, d_words);
+  int rc = partition_words(c, d_words, nwords, &dst);
   c->staged = dst;
   return finish(c, rc);
 }
@@ -2039,7 +2017,7 @@ extern "C" int shk_insert_counted(shk_ctx *c, const uint64_t *keys, const uint64
       { ProfScope ps(c, KP_MISC);
         hipLaunchKernelGGL(k_expand_counted<0>, dim3(nb), dim3(256), 0, c->stream, dk + done, dc + done, m, skip, take, c->cfg.hb, dnw,
                            (const uint64_t *)nullptr, (uint64_t *)nullptr, c->d_err, key_lo, key_hi, (unsigned long long *)(c->d_scalars + 4)); }
-      if (run_scan<uint32_t>(c, dnw, m, nullptr, doff)) { rc = SHK_ERR_HIP; break; }
+      if (run_scan<uint32_t>(c, c, dnw, m, nullptr, doff)) { rc = SHK_ERR_HIP; break; }
       HIPCHK(hipMemcpyAsync(c->h_pinned + 45, doff + m, 8, hipMemcpyDeviceToHost, c->stream));
       HIPCHK(hipMemcpyAsync(c->h_pinned + 46, c->d_scalars + 4, 8, hipMemcpyDeviceToHost, c->stream));
       uint32_t bits = 0;
@@ -2055,7 +2033,7 @@ extern "C" int shk_insert_counted(shk_ctx *c, const uint64_t *keys, const uint64
         c->h_pinned[43] = nwords;
         HIPCHK(hipMemcpyAsync(c->d_scalars + 1, c->h_pinned + 43, 8, hipMemcpyHostToDevice, c->stream));
         int dst = 0;
-        rc = partition_stage(c, 0, nwords, &dst);
+        rc = partition_stage(c, c, 0, nwords, &dst);
         if (rc) break;
         MergeOut o;
         rc = merge_plain(c, c->d_words[dst], &o);
@@ -2106,7 +2084,7 @@ extern "C" int shk_dump(shk_ctx *c, uint64_t *keys, uint64_t *counts, uint64_t c
     if (bits) { prof_collect(c); return map_err_bits(bits); }
     break;
   }
-  if (run_scan<uint32_t>(c, nper, c->nregions, nullptr, offs)) return SHK_ERR_HIP;
+  if (run_scan<uint32_t>(c, c, nper, c->nregions, nullptr, offs)) return SHK_ERR_HIP;
   HIPCHK(hipMemcpyAsync(c->h_pinned + 45, offs + c->nregions, 8, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   const uint64_t total = c->h_pinned[45];
@@ -2265,7 +2243,8 @@ extern "C" int shk_select_seeds(shk_ctx *c, const void *text, int text_on_device
   HIPCHK(hipSetDevice(c->dev));
   const uint8_t *dtext;
   uint64_t nreads;
-  int rc = parse_stage(c, text, text_on_device, text_bytes, chunk_off, chunk_len, nchunks, &dtext, &nreads);
+  if (upload_wait(c, text, text_on_device, c->stream)) return SHK_ERR_HIP;
+  int rc = parse_stage(c, c, text, text_on_device, text_bytes, chunk_off, chunk_len, nchunks, &dtext, &nreads);
   if (rc) return finish(c, rc);
   *n_out = 0;
   if (nreads == 0) return finish(c, 0);
@@ -2605,7 +2584,8 @@ extern "C" int shk_unitigs_add_reads(shk_ctx *c, shk_unitig_set *u, const void *
   if (rc) return rc;
   const uint8_t *dtext;
   uint64_t nreads;
-  rc = parse_stage(c, text, text_on_device, text_bytes, chunk_off, chunk_len, nchunks, &dtext, &nreads);
+  if (upload_wait(c, text, text_on_device, c->stream)) return SHK_ERR_HIP;
+  rc = parse_stage(c, c, text, text_on_device, text_bytes, chunk_off, chunk_len, nchunks, &dtext, &nreads);
   if (rc) return finish(c, rc);
   if (nseeds) *nseeds = 0;
   if (nreads == 0) return finish(c, 0);
@@ -2697,7 +2677,7 @@ extern "C" int shk_unitig_set_write(shk_unitig_set *u, uint32_t k, const char *o
       for (uint32_t i = 1; i < n; i++)
         if ((hp[i] & 15) == SHK_STOP_CIRCLE) fprintf(stderr, "SHK_UG_DEBUG circle id %u state %d keep %u len %u hmin %016llx\n", i, hs[i], hkeep[i], hl[i], (unsigned long long)hh[i]);
     }
-    if (run_scan<uint32_t>(c, d_keep, n, nullptr, d_newid, d_sums) || run_scan<uint32_t>(c, d_lens, n, nullptr, d_off, d_sums)) { rc = SHK_ERR_HIP; break; }
+    if (run_scan<uint32_t>(c, c, d_keep, n, nullptr, d_newid, d_sums) || run_scan<uint32_t>(c, c, d_lens, n, nullptr, d_off, d_sums)) { rc = SHK_ERR_HIP; break; }
     if (hipMemcpyAsync(c->h_pinned + 45, d_newid + n, 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
         hipMemcpyAsync(c->h_pinned + 46, d_off + n, 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
         hipStreamSynchronize(c->stream) != hipSuccess) { rc = SHK_ERR_HIP; break; }
