@@ -105,7 +105,12 @@ void shk_destroy(shk_ctx *ctx);
 /* Count every k-mer of `nchunks` FASTQ chunks. chunk_off/chunk_len index into `text`
  * (text_on_device != 0: `text` is a device pointer, 16-byte aligned, that stays valid until the call returns; the
  * kernels read the text in aligned 16-byte units, so the allocation must be readable up to the next multiple of 16
- * behind text + text_bytes -- hipMalloc'ed buffers always are).
+ * behind text + text_bytes -- hipMalloc'ed buffers always are. Every call that takes device text answers a pointer
+ * that is not 16-byte aligned with SHK_ERR_ARG before it starts anything).
+ * The chunks may lie in any order, leave bytes of the text out, be shorter than 16 bytes or empty (chunk_len 0: no
+ * reads); lines are counted from each chunk's own first byte. One call takes 1 .. 4096 chunks (SHK_ERR_BATCH otherwise;
+ * so do shk_prepare_chunks, shk_hash_chunks and shk_hash_route_chunks, whose labels must stay below 4096 too). A read of
+ * more than 65535 bases is SHK_ERR_FASTQ from each of them, the table left as it was.
  * Chunks are the units after which the reference tests its deNoise trigger; rounds fire
  * inside the call exactly where the t = 1 reference would fire them. */
 int shk_count_chunks(shk_ctx *ctx, const void *text, int text_on_device, uint64_t text_bytes,

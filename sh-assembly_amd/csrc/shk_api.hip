@@ -411,8 +411,11 @@ static bool chunk_labels_ok(uint32_t nchunks, uint32_t chunk_first, uint32_t chu
 }
 
 // text -> extents of every read (d_rd_start, d_rd_end, d_rd_chunk); *dtext_out = where the text is on the device
+// (device text: k_count_lines, k_emit_reads and k_count_keys fetch 16-byte units at multiples of 16 from the text's base)
+static bool text_aligned(const void *text, int on_device) { return !on_device || ((uintptr_t)text & 15) == 0; }
 static int parse_stage(const shk_ctx *c, ShkStageBufs *b, const void *text, int on_device, uint64_t text_bytes, const uint64_t *chunk_off,
                        const uint64_t *chunk_len, uint32_t nchunks, const uint8_t **dtext_out, uint64_t *nreads_out) {
+  if (!text_aligned(text, on_device)) return SHK_ERR_ARG;
   for (uint32_t i = 0; i < nchunks; i++)
     if (chunk_off[i] + chunk_len[i] > text_bytes) return SHK_ERR_ARG;
   const uint8_t *dtext;
@@ -447,8 +450,9 @@ static int hash_stage(const shk_ctx *c, ShkStageBufs *b, const void *text, int o
                       const uint64_t *chunk_len, uint32_t nchunks, uint32_t chunk_first, uint32_t chunk_mul, bool hist0 = false) {
   // chunk i of this call is labelled chunk_first + i * chunk_mul; hist0: the hash kernel also fills the first partition
   // level's histogram (d_hist[0]), see partition_stage
-  if (hist0) HIPCHK(hipMemsetAsync(b->d_hist[0], 0, (1ULL << (c->lv[0].bits + c->lv[0].ng_log2)) * 8, b->stream));
   if (!chunk_labels_ok(nchunks, chunk_first, chunk_mul)) return SHK_ERR_BATCH;
+  if (!text_aligned(text, on_device)) return SHK_ERR_ARG;
+  if (hist0) HIPCHK(hipMemsetAsync(b->d_hist[0], 0, (1ULL << (c->lv[0].bits + c->lv[0].ng_log2)) * 8, b->stream));
   const uint8_t *dtext;
   uint64_t nreads;
   { int rc = parse_stage(c, b, text, on_device, text_bytes, chunk_off, chunk_len, nchunks, &dtext, &nreads); if (rc) return rc; }
@@ -1385,7 +1389,8 @@ static void front_run(const shk_ctx *c, ShkFrontSlot *S, const void *text, int o
 
 extern "C" int shk_prepare_chunks(shk_ctx *c, const void *text, int text_on_device, uint64_t text_bytes, const uint64_t *chunk_off,
                                   const uint64_t *chunk_len, uint32_t nchunks) {
-  if (!c || !text || !chunk_off || !chunk_len || nchunks == 0 || nchunks > SHK_MAX_CHUNKS) return SHK_ERR_ARG;
+  if (!c || !text || !chunk_off || !chunk_len || !text_aligned(text, text_on_device)) return SHK_ERR_ARG;
+  if (!chunk_labels_ok(nchunks, 0, 1)) return SHK_ERR_BATCH;   // (as shk_count_chunks answers it)
   if (c->cfg.num_shards > 1) return SHK_ERR_ARG;          // (a shard's words go through the exchange: shk_hash_chunks)
   HIPCHK(hipSetDevice(c->dev));
   if (!c->front) { int rc = front_init(c); if (rc) { front_destroy(c); return rc; } }

@@ -351,3 +351,38 @@ def test_oracle_vs_reference_reads_with_bytes_that_are_no_base():
         keys = O.chunk_keys(fq, k, 22)
         assert len(keys) == o.nelts()
         o.free(), r.free()
+
+
+@needs_ref
+def test_oracle_vs_reference_front_end_text_shapes():
+    """every text of tests/text_cases.py that the reference's reads_to_kmers survives (whole groups of four lines per
+    chunk: it does not test its memchr results, CQF_mt.h:616-620, 723-726) through the oracle and the compiled reference,
+    chunk by chunk: equal keys with equal counts and equal table bytes. Reads of up to 65535 bases, 'N' restarts far behind
+    base 256, neighbours that look like bases, empty lines, CRLF, a lone '\\r', chunk tables in any order and with gaps.
+    The other texts (cut-off records, chunks of one to three lines) have no reference behaviour to compare with: the
+    reference reads through a null pointer there; the oracle stops at the failed memchr."""
+    import text_cases as TC
+    R = cqflibs.ref()
+    texts = TC.all_texts()
+    safe = [T for T in texts if T.ref_safe()]
+    names = {T.name for T in safe}
+    assert set(TC.LONG_NAMES) <= names and "lines-empty-sequence-line" in names and "lines-crlf-k47-per1" in names
+    assert "chunks-with-gaps" in names and "lines-lone-cr-in-read" in names
+    assert sorted(T.name for T in texts if not T.ref_safe()) == sorted(
+        ["lines-" + n for n in ("no-final-newline", "cut-inside-quality", "stops-after-sequence-line", "stops-inside-sequence-line",
+                                "stops-after-plus-newline", "stops-after-plus", "stops-after-header",
+                                "newline-chunks-and-short-chunks")] + ["chunks-of-1-to-15-bytes-and-empty"])
+    for T in safe:
+        o, r = O.new(T.qb), R.new(T.qb)
+        for c in T.chunks():
+            o.reads_to_kmers(c, T.k), r.reads_to_kmers(c, T.k)
+        assert o.blocks() == r.blocks() and o.nelts() == r.nelts() and o.ndistinct() == r.ndistinct(), T.name
+        assert o.dump() == r.dump(), T.name
+        words, blocks, _, nelts, _ = T.expected()
+        assert blocks == o.blocks() and nelts == o.nelts(), T.name
+        hb = T.qb + 8
+        tally = {}
+        for w in words:
+            tally[w & ((1 << hb) - 1)] = tally.get(w & ((1 << hb) - 1), 0) + 1
+        assert sorted(tally.items()) == o.dump(), T.name
+        o.free(), r.free()

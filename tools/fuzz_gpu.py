@@ -14,6 +14,9 @@ def main():
     ap.add_argument("--max-qb", type=int, default=17)
     ap.add_argument("--qbs", default="", help="comma-separated filter sizes to draw from (default 11..max-qb)")
     ap.add_argument("--max-reads", type=int, default=4000)
+    ap.add_argument("--long-reads", action="store_true", help="add two or three reads of 600 .. 20000 bases to every case, on a filter of qb 17 "
+                    "(whatever --max-qb says) so that they fit, and fill the quality lines with 'N' or '@' (drawn from a generator of their own: "
+                    "the default draw, and so what a seed means, stays as it is)")
     args = ap.parse_args()
     lib = os.path.join(ROOT, "tests", "emu", "libshk_emu.so") if args.emu else None
     import torch  # noqa: F401  (torch's HIP runtime first)
@@ -27,6 +30,7 @@ def main():
         dev = torch.device("cpu" if args.emu else "cuda:0")
     rnd = random.Random(args.seed)
     bad = skipped = 0
+    long_stats = [0, 0, 0]      # --long-reads: reads added, of them above 10000 bases, the longest
     t0 = time.time()
     for case in range(args.cases):
         qb = rnd.choice([int(x) for x in args.qbs.split(",")] if args.qbs else [q for q in (11, 12, 13, 14, 15, 16, 17) if q <= args.max_qb])
@@ -43,6 +47,27 @@ def main():
         fq = synth.make_fastq(synth.make_genome(G, rnd.randrange(1 << 30)), nreads, L, err, seed=rnd.randrange(1 << 30),
                               n_frac=rnd.choice([0.0, 0.02, 0.2]), short_frac=rnd.choice([0.0, 0.05]), lower_frac=rnd.choice([0.0, 0.05]),
                               iupac_frac=rnd.choice([0.0, 0.0, 0.1]))
+        if args.long_reads:
+            xr = random.Random((args.seed << 20) + case)
+            lines = fq.split(b"\n")[:-1]
+            for i in range(3, len(lines), 4):
+                lines[i] = xr.choice([b"N", b"@", b"I"]) * len(lines[i])
+            # the default draw's reads fill at most 0.45 of the filter it drew; two or three reads of up to 20000 bases (all
+            # their k-mers distinct) are another 0.46 of 2^17 slots at the most: a filter of qb 17, or 18 if that was drawn at 17
+            qb = 17 if qb < 17 else 18
+            cap = int((1 << qb) * 0.45)
+            for _ in range(xr.choice([2, 3])):
+                n = xr.randrange(600, 20001)
+                long_stats[0] += 1
+                long_stats[1] += n > 10000
+                long_stats[2] = max(long_stats[2], n)
+                seq = bytearray(xr.choices(b"ACGT", k=n))
+                for _ in range(xr.choice([0, 0, 1, n // 500])):
+                    seq[xr.randrange(n)] = ord("N")
+                at = 4 * xr.randrange(len(lines) // 4 + 1)
+                lines[at:at] = [b"@long%d" % n, bytes(seq), b"+", xr.choice([b"N", b"@"]) * n]
+            fq = b"\n".join(lines) + b"\n"
+            nreads = len(lines) // 4
         per = max(1, nreads // rnd.choice([1, 3, 7, 20]))
         offs, lens = chunks_by_records(fq, per)
         nd = rnd.choice([0, 1, 2, 3, 6])
@@ -72,13 +97,14 @@ def main():
         scheme = rnd.choice([None] * 2 + ["SHK_NO_FUSED_POINT", "SHK_RP_NO_GROUPS"])
         if scheme:
             os.environ[scheme] = "1"
+        keys_cap = len(fq) // 2 + 64 if args.long_reads else nreads * L + 64
         if args.sharded:
-            ctx = shk.Context(qb=qb, k=k, min_denoise_len=ml, max_batch_bytes=len(fq) + 1024, max_batch_keys=nreads * L + 64,
+            ctx = shk.Context(qb=qb, k=k, min_denoise_len=ml, max_batch_bytes=len(fq) + 1024, max_batch_keys=keys_cap,
                               shard_index=0, num_shards=1, max_level_bits=mlb, lib_path=lib)
             sst = shkdist.ShardState(trig, nd, dev)
         else:
             ctx = shk.Context(qb=qb, k=k, trigger=trig, num_denoise=nd, min_denoise_len=ml, max_batch_bytes=len(fq) + 1024,
-                              max_batch_keys=nreads * L + 64, max_level_bits=mlb, lib_path=lib)
+                              max_batch_keys=keys_cap, max_level_bits=mlb, lib_path=lib)
         ncalls = rnd.choice([1, 2, 3, len(offs)])
         step = max(1, (len(offs) + ncalls - 1) // ncalls)
         rounds = removed = 0
@@ -120,6 +146,8 @@ def main():
         ctx.close()
         q.free()
     print(f"fuzz: {args.cases} cases ({skipped} skipped: the oracle's table was full), {bad} mismatches, {time.time() - t0:.0f} s")
+    if args.long_reads:
+        print(f"long reads: {long_stats[0]} in {args.cases} cases, {long_stats[1]} above 10000 bases, longest {long_stats[2]}")
     if args.sharded:
         dist.destroy_process_group()
     sys.exit(1 if bad else 0)
