@@ -290,9 +290,13 @@ int shk_import_shards(shk_ctx *ctx, const void *const *shard_blocks, const uint6
 int shk_stats(shk_ctx *ctx, shk_totals *out);
 /* 128-byte quotient_filter_metadata image (gqf.h:62-77) for this context */
 int shk_header(shk_ctx *ctx, uint8_t out[128]);
-/* table bytes (nblocks * 89) to host memory */
+/* table bytes (nblocks * 89) to host memory. Counting calls commit lazily: they keep the rebuilt runs as per-region
+ * records and leave the table's bytes unwritten until a call reads them, so this call (like every other reader: lookup,
+ * dump, export, merge, the Contiger calls, shk_denoise) may first launch the placement kernel, once per build rather than
+ * once per batch. SHK_LAZY_PLACE=0 in the environment of shk_create makes every counting call write the table itself. */
 int shk_export_blocks(shk_ctx *ctx, void *host_dst, uint64_t cap);
-/* device pointer and size of the live table (valid until the next call that rebuilds the table) */
+/* device pointer and size of the live table; may launch the placement (see shk_export_blocks) and synchronises. The
+ * pointer is valid until the next counting call (any call that rebuilds the table): the two table buffers alternate. */
 int shk_table_ptr(shk_ctx *ctx, void **d_table, uint64_t *nbytes);
 /* header + blocks, byte-identical to qf_serialize */
 int shk_export_cqf(shk_ctx *ctx, const char *path);

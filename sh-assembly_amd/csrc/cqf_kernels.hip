@@ -54,6 +54,7 @@ struct ShkMergeArgs {
   // spill scheme (MODE 3 -> k_region_scan_* -> k_region_place): the summary launch keeps every region's
   // run lengths and encoded bytes so that the second launch only places them
   uint8_t *spill;                 // [nregions * SHK_SPILL_STRIDE]
+  const uint8_t *orec;            // OLDREC instantiations: the records the previous pass spilled, read in place of table A
   uint32_t *over_list;            // regions whose runs did not fit the spill record (rebuilt by MODE 1 from this list)
   unsigned long long *n_over;
   const uint32_t *list;           // regions to rebuild (null = all: region = blockIdx.x + r0)
@@ -147,6 +148,32 @@ __device__ __forceinline__ unsigned shk_img_dec_fast(const uint8_t *img, unsigne
   return shk_img_dec(img, pos, run_end, rem_out, count);
 }
 
+// The same two decoders over contiguous bytes: the packed run bytes of a spill record, where slot p is byte p and a run
+// ends where its length ends (the OLDREC instantiations of k_region_merge)
+__device__ __forceinline__ unsigned shk_flat_dec(const uint8_t *s, unsigned pos, unsigned run_end, unsigned *rem_out, uint64_t *count) {
+  unsigned rem = s[pos];
+  *rem_out = rem;
+  if (pos == run_end) { *count = 1; return 1; }
+  unsigned digit = s[pos + 1];
+  if (digit > rem) { *count = 1; return 1; }
+  unsigned n = 1;
+  uint64_t cnt = 0;
+  if (digit == 0) { n++; digit = s[pos + n]; }
+  while ((digit & 0x80) && pos + n < run_end) { cnt = cnt * 128 + (digit & 0x7f); n++; digit = s[pos + n]; }
+  cnt = cnt * 128 + (digit & 0x7f);
+  *count = cnt + 1;
+  return n + 1;
+}
+__device__ __forceinline__ unsigned shk_flat_dec_fast(const uint8_t *s, unsigned pos, unsigned run_end, unsigned *rem_out, uint64_t *count) {
+  const unsigned rem = s[pos];
+  *rem_out = rem;
+  if (pos == run_end) { *count = 1; return 1; }
+  const unsigned d = s[pos + 1];
+  if (d > rem) { *count = 1; return 1; }
+  if (d != 0 && d < 0x80) { *count = (uint64_t)d + 1; return 2; }
+  return shk_flat_dec(s, pos, run_end, rem_out, count);
+}
+
 // ---- image -> table B (shared by the rebuild kernel's write modes and k_region_place)
 template <int IMGB>
 __device__ __forceinline__ void shk_store_image(const ShkMergeArgs &A, uint32_t r, uint32_t nregions, const uint8_t *nimg,
@@ -212,9 +239,14 @@ __device__ __forceinline__ void shk_store_image(const ShkMergeArgs &A, uint32_t 
 
 #define SHK_STAMP(i) do { if (A.dbg && (blockIdx.x & 63) == 0 && threadIdx.x == 0) { unsigned long long t_ = __builtin_amdgcn_s_memtime(); atomicAdd(&A.dbg[i], t_ - t_prev); t_prev = t_; } } while (0)
 
-template <int MODE, int IMGB, bool FUSED = false>
+// OLDREC: the old runs come from the region's previous spill record (A.orec: 256 length bytes + the runs' bytes back to
+// back in quotient order) instead of its blocks of table A, which then need not exist (lazy placement, shk_api.hip). No
+// image, no rank/select: a lane's four length bytes say which of its quotients have a run, a wave sum of the lanes' byte
+// totals where its first run starts. Not for the write pass, nor for a deNoise round that reads traveled bits.
+template <int MODE, int IMGB, bool FUSED = false, bool OLDREC = false>
 __global__ void __launch_bounds__(SHK_MERGE_GROUP) k_region_merge(ShkMergeArgs A) {
   static_assert(!FUSED || MODE == 3, "the one-pass deNoise point is a spill-mode pass");
+  static_assert(!OLDREC || MODE == 0 || MODE == 3, "the write pass reads the table");
   constexpr bool WRITE = MODE == 1;                // builds the image and stores table B
   constexpr bool STAGE = WRITE || MODE == 3;       // keeps the runs' encodings per lane
   // LDS image of IMGB blocks: the region's own blocks + the blocks its runs may spill into.
@@ -238,6 +270,7 @@ __global__ void __launch_bounds__(SHK_MERGE_GROUP) k_region_merge(ShkMergeArgs A
   __shared__ uint16_t rstart[SHK_REGION];
   __shared__ __attribute__((aligned(16))) uint8_t oimg[IMG_BYTES + 16];
   __shared__ __attribute__((aligned(16))) uint8_t nimg[IMG_BYTES + 16];
+  __shared__ __attribute__((aligned(16))) uint8_t opk[SHK_SPILL_PACK_MAX + 16];   // OLDREC: the old runs' bytes
   __shared__ __attribute__((aligned(16))) uint8_t stage[SHK_MERGE_THREADS * SHK_STAGE_STRIDE];
   __shared__ uint64_t oocc[SHK_REGION_BLOCKS];
   __shared__ uint64_t orunw[IMG_BLOCKS];
@@ -273,7 +306,7 @@ __global__ void __launch_bounds__(SHK_MERGE_GROUP) k_region_merge(ShkMergeArgs A
   // hash slots in use, in order of first insertion (lives in `stage`, which is idle until the merge pass)
   uint16_t *slist = reinterpret_cast<uint16_t *>(stage);
   bool fatal = false;
-  if (nblk_old > IMG_BLOCKS || ohi > IMG_SLOTS) {
+  if (!OLDREC && (nblk_old > IMG_BLOCKS || ohi > IMG_SLOTS)) {
     if (tid == 0) atomicOr(A.err, SHK_E_OLD_EXTENT);
     fatal = true;
     nblk_old = nown;
@@ -293,11 +326,28 @@ __global__ void __launch_bounds__(SHK_MERGE_GROUP) k_region_merge(ShkMergeArgs A
   }
 
   // ---- stage the old bytes (dword copies; the region's first byte is 4-byte aligned)
+  uint32_t ol4 = 0, oex = 0;      // OLDREC: my four old run lengths (one byte each), where my first old run's bytes start
+  bool orec_bad = false;
   {
+    if (OLDREC) {
+      // the first wave, which goes on to merge, keeps its length bytes and copies as many packed bytes as they add up to
+      if (tid < SHK_WAVE) {
+        const uint32_t *src = reinterpret_cast<const uint32_t *>(A.orec + (size_t)r * SHK_SPILL_STRIDE);
+        ol4 = src[tid];
+        const uint32_t mine = (ol4 & 255u) + ((ol4 >> 8) & 255u) + ((ol4 >> 16) & 255u) + (ol4 >> 24);
+        const uint32_t sincl = shk_wave_incl_add(mine);
+        oex = sincl - mine;
+        uint32_t ototal = (uint32_t)__builtin_amdgcn_readlane((int)sincl, SHK_WAVE - 1);
+        if (ototal > SHK_SPILL_PACK_MAX) { orec_bad = true; ototal = 0; ol4 = 0; }   // (not a record this library wrote)
+        uint32_t *dst = reinterpret_cast<uint32_t *>(opk);
+        for (uint32_t i = tid; i < (ototal + 3) / 4; i += SHK_WAVE) dst[i] = src[SHK_SPILL_LENS / 4 + i];
+      }
+    } else {
     const uint32_t nbytes = nblk_old * SHK_BLOCK_BYTES;
     const uint32_t *src = reinterpret_cast<const uint32_t *>(A.tabA + b0 * SHK_BLOCK_BYTES);
     uint32_t *dst = reinterpret_cast<uint32_t *>(oimg);
     if (!(A.ablate & 64)) for (uint32_t i = tid; i < (nbytes + 3) / 4; i += ngrp) dst[i] = src[i];
+    }
     // (16-byte LDS stores: the LDS pipeline, shared by all waves of the CU, is what this kernel keeps busiest)
     {
       const uint4 e4 = make_uint4(SHK_EMPTY, SHK_EMPTY, SHK_EMPTY, SHK_EMPTY), z4 = make_uint4(0, 0, 0, 0);
@@ -395,9 +445,9 @@ __global__ void __launch_bounds__(SHK_MERGE_GROUP) k_region_merge(ShkMergeArgs A
   // OLD runs (rank/select over the staged blocks) and the grouping of the NEW keys by quotient. The second wave of the
   // group takes the first while the first wave does the second (a group of one wave does both); barriers inside the
   // two parts are wave-local. Then the helper leaves and one wave carries on.
-  if (tid >= 2 * nthr) return;
+  if (tid >= (OLDREC ? 1 : 2) * nthr) return;     // (OLDREC: no old structure to prepare, the helper leaves here)
   const bool helper = ngrp > nthr && tid >= nthr;
-  if (helper || ngrp == nthr) {
+  if (!OLDREC && (helper || ngrp == nthr)) {
     // ---- old structure: occupieds of the own blocks, runends inside [olo, ohi)
     const unsigned ln = tid & (SHK_WAVE - 1);
     {
@@ -479,8 +529,10 @@ __global__ void __launch_bounds__(SHK_MERGE_GROUP) k_region_merge(ShkMergeArgs A
     }
   }
   // (each lane sorted only its own quotients' segments)
-  __syncthreads();                       // join: the old structure is in place (the helper wave leaves here)
+  if (OLDREC) shk_wave_sync();
+  else __syncthreads();                  // join: the old structure is in place (the helper wave leaves here)
   if (s_fail & SHK_E_CORRUPT) fatal = true;
+  if (OLDREC && orec_bad) { fatal = true; if (tid == 0) atomicOr(A.err, SHK_E_CORRUPT); }
 
   SHK_STAMP(3);   // counting sort + per-quotient sort
   // ---- one pass over the quotients: merge old run and new keys -> run length, statistics,
@@ -498,20 +550,40 @@ __global__ void __launch_bounds__(SHK_MERGE_GROUP) k_region_merge(ShkMergeArgs A
   // of its runs on one side, its new keys (nidx is sorted the same way) on the other. A wave runs the
   // loop as often as its busiest lane has entries -- about half of what four per-quotient loops cost.
   if (qa < nq && !fatal && !(A.ablate & 2)) {
-    const uint64_t ow = oocc[qa >> 6];
+    static_assert(!OLDREC || per == 4, "a lane's length bytes are one dword of the record");
+    const uint64_t ow = OLDREC ? 0 : oocc[qa >> 6];
     uint32_t occ4 = (uint32_t)(ow >> (qa & 63)) & ((1u << per) - 1);          // which of my quotients had a run
-    uint32_t jr = oorank[qa >> 6] + (uint32_t)__popcll(ow & ((1ULL << (qa & 63)) - 1));  // index of my first old run
-    uint32_t oprev = jr ? (uint32_t)orend[jr - 1] + 1 : olo;                  // first slot behind the previous old run
+    uint32_t jr = OLDREC ? 0 : oorank[qa >> 6] + (uint32_t)__popcll(ow & ((1ULL << (qa & 63)) - 1));  // index of my first old run
+    uint32_t oprev = OLDREC ? 0 : (jr ? (uint32_t)orend[jr - 1] + 1 : olo);   // first slot behind the previous old run
     uint32_t oq = 0, opos = 0, oend = 0, orem = 0, on = 0;
     uint64_t ocnt = 0;
     bool ohas = false;
-    if (occ4) {
-      oq = qa + (uint32_t)__ffs((int)occ4) - 1; occ4 &= occ4 - 1;
-      oend = orend[jr];
-      opos = oprev > oq ? oprev : oq;
-      on = shk_img_dec_fast(oimg, opos, oend, &orem, &ocnt);
-      ohas = true;
+    // The old side's cursor, the one place where the two sources differ. Table: positions are slots of the image, a run
+    // starts at its quotient or behind the previous run and ends at its runend. Records: positions are byte offsets
+    // into opk, my runs lie back to back from oex on, each as long as its length byte says.
+    auto old_decode = [&]() {                // the entry at opos
+      on = OLDREC ? shk_flat_dec_fast(opk, opos, oend, &orem, &ocnt) : shk_img_dec_fast(oimg, opos, oend, &orem, &ocnt);
+    };
+    auto old_open_run = [&]() {              // the run of my lowest quotient that is left (occ4 != 0), at its first entry
+      const uint32_t j = (uint32_t)__ffs((int)occ4) - 1;
+      oq = qa + j; occ4 &= occ4 - 1;
+      if (OLDREC) oend = opos + ((ol4 >> (8 * j)) & 255u) - 1;               // (opos: behind my previous run's bytes)
+      else { oend = orend[jr]; opos = oprev > oq ? oprev : oq; }
+      old_decode();
+    };
+    auto old_next = [&]() {                  // behind the entry just taken: the rest of its run, my next run, or nothing
+      opos += on;
+      if (opos <= oend) old_decode();
+      else if (occ4) {
+        if (!OLDREC) { jr++; oprev = oend + 1; }
+        old_open_run();
+      } else ohas = false;
+    };
+    if (OLDREC) {
+      occ4 = ((ol4 & 0xFFu) ? 1u : 0u) | ((ol4 & 0xFF00u) ? 2u : 0u) | ((ol4 & 0xFF0000u) ? 4u : 0u) | ((ol4 >> 24) ? 8u : 0u);
+      opos = oex;
     }
+    if (occ4) { old_open_run(); ohas = true; }
     uint32_t ni = qoff[qa];
     const uint32_t ne = qoff[qa + per];
     uint32_t nh = 0, nkey = 0;
@@ -543,18 +615,7 @@ __global__ void __launch_bounds__(SHK_MERGE_GROUP) k_region_merge(ShkMergeArgs A
       if (FUSED) {
         // one-pass deNoise point: cb = the key's count when the round runs (old + chunks <= split), ca = what arrives behind it
         uint64_t cb = take_old ? ocnt : 0, ca = 0;
-        if (take_old) {
-          opos += on;
-          if (opos <= oend) on = shk_img_dec_fast(oimg, opos, oend, &orem, &ocnt);
-          else if (occ4) {
-            oq = qa + (uint32_t)__ffs((int)occ4) - 1; occ4 &= occ4 - 1;
-            jr++;
-            oprev = oend + 1;
-            oend = orend[jr];
-            opos = oprev > oq ? oprev : oq;
-            on = shk_img_dec_fast(oimg, opos, oend, &orem, &ocnt);
-          } else ohas = false;
-        }
+        if (take_old) old_next();
         if (take_new) {
           { const uint32_t c2 = hcnt[nh]; cb += c2 & 0xFFFFu; ca = c2 >> 16; }
           if (A.newchunks && !take_old) hcnt[nh] = 0x80000000u;   // a key the table has not seen: its first chunk is collected below (the counts are consumed)
@@ -580,23 +641,14 @@ __global__ void __launch_bounds__(SHK_MERGE_GROUP) k_region_merge(ShkMergeArgs A
       } else {
       if (take_old) {
         total = ocnt;
-        if (A.denoise) {
+        if (!OLDREC && A.denoise) {
           // a deNoise round drops the OLD singleton unless k_denoise_marks protected it (traveled bit in table A);
           // words of this pass (chunks behind the deNoise point) then count as if the key had never been seen
           const uint32_t tb = (opos >> 6) * SHK_BLOCK_BYTES + SHK_OFF_TRAV + ((opos & 63) >> 3);
           const bool prot = (oimg[tb] >> (opos & 7)) & 1;
           if (ocnt < 2 && !prot) { my_removed++; total = 0; is_new = true; }
         }
-        opos += on;
-        if (opos <= oend) on = shk_img_dec_fast(oimg, opos, oend, &orem, &ocnt);
-        else if (occ4) {                    // my next old run
-          oq = qa + (uint32_t)__ffs((int)occ4) - 1; occ4 &= occ4 - 1;
-          jr++;
-          oprev = oend + 1;
-          oend = orend[jr];
-          opos = oprev > oq ? oprev : oq;
-          on = shk_img_dec_fast(oimg, opos, oend, &orem, &ocnt);
-        } else ohas = false;
+        old_next();
       } else is_new = true;
       if (take_new) {
         total += hcnt[nh];
@@ -847,19 +899,14 @@ __global__ void __launch_bounds__(SHK_WAVE) k_region_place(ShkMergeArgs A) {
   const unsigned tid = threadIdx.x;
   const uint32_t r = blockIdx.x + A.r0;
   const uint32_t nregions = (uint32_t)((A.nslots + SHK_REGION - 1) / SHK_REGION);
-  const uint32_t *sm = A.summary + (size_t)SHK_SUM_STRIDE * r;
-  if (sm[6]) return;
+  // (A.summary null: the records of a committed pass, placed later -- none of its regions went to the over list)
+  if (A.summary && A.summary[(size_t)SHK_SUM_STRIDE * r + 6]) return;
   const uint64_t q0 = (uint64_t)r * SHK_REGION;
   const uint32_t nq = (uint32_t)((A.nslots - q0) < SHK_REGION ? (A.nslots - q0) : SHK_REGION);
   const uint32_t nown = (nq + 63) / 64;
   const uint64_t b0 = q0 / 64;
-  const bool new_any = sm[0] > 0;
   const long long fin_rel = (long long)A.finB[r] - (long long)q0;
   const long long fout_rel = (long long)A.finB[r + 1] - (long long)q0;
-  if (new_any && (fout_rel > IMG_SLOTS || fout_rel < 0)) {
-    if (tid == 0) atomicOr(A.err, SHK_E_NEW_EXTENT);
-    return;
-  }
   const uint8_t *sp = A.spill + (size_t)r * SHK_SPILL_STRIDE;
   const uint32_t l4 = reinterpret_cast<const uint32_t *>(sp)[tid];
   {
@@ -888,6 +935,11 @@ __global__ void __launch_bounds__(SHK_WAVE) k_region_place(ShkMergeArgs A) {
   const uint32_t sinc = shk_wave_incl_add(st_used);
   const uint32_t ex = sinc - st_used;
   const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)sinc, SHK_WAVE - 1);
+  const bool new_any = total > 0;                        // (= the region's T: every run's bytes are in the record)
+  if ((new_any && (fout_rel > IMG_SLOTS || fout_rel < 0)) || total > SHK_SPILL_PACK_MAX) {
+    if (tid == 0) atomicOr(A.err, total > SHK_SPILL_PACK_MAX ? SHK_E_CORRUPT : SHK_E_NEW_EXTENT);
+    return;
+  }
   {
     const uint32_t *src = reinterpret_cast<const uint32_t *>(sp + SHK_SPILL_LENS);
     uint32_t *dst = reinterpret_cast<uint32_t *>(pack);

@@ -101,7 +101,14 @@ struct shk_ctx : ShkStageBufs {
   int big_image;                // 1: rebuild kernels run with the SHK_IMG_BLOCKS_BIG image (set after a cluster outgrew the small one)
   uint32_t merge_group;         // threads per region workgroup (one wave rebuilds; the others help staging and folding)
   // the summary launch spills lengths + encodings per region, k_region_place writes table B from them
-  uint8_t *d_spill;
+  // Lazy placement: a clean pass is committed by keeping its records (and the free pointers of its scan) as the truth;
+  // the next pass reads them as its old side (the OLDREC instantiations of k_region_merge) and writes the other buffer;
+  // the table's bytes are produced when somebody looks at them (table_sync).
+  uint8_t *spill[2];            // a pass writes spill_out(); [1] is allocated by the first lazy commit or a *_reserve call
+  int live;                     // which of the two buffers holds the records of the last lazy commit
+  int rec_live;                 // 1: spill[live] + fin[cur] describe the live table (a pass may take its old side from them)
+  int table_stale;              // 1: tab[cur] has not been written from them yet, or its placement failed (implies rec_live)
+  int lazy_ok;                  // 0: every commit places (SHK_LAZY_PLACE=0, or the second record buffer did not fit)
   uint32_t *d_over_list;
   // what the spill records currently describe (a write pass may use them only for the same request)
   int spill_valid; const uint64_t *spill_words; uint32_t spill_lo, spill_hi; int spill_denoise, spill_big;
@@ -309,7 +316,9 @@ static int create_init(shk_ctx *c, const shk_config *cfg) {
   c->sample_stride = c->nregions >= (1u << 20) ? 16 : 8;
   if (const char *e = getenv("SHK_SAMPLE_STRIDE")) c->sample_stride = (uint32_t)atoi(e);
   else if (c->nregions < (1u << 14)) c->sample_stride = 0;
-  if (dmalloc(&c->d_spill, (uint64_t)c->nregions * SHK_SPILL_STRIDE) || dmalloc(&c->d_over_list, (uint64_t)c->nregions + 1)) return SHK_ERR_HIP;
+  c->lazy_ok = 1;
+  if (const char *e = getenv("SHK_LAZY_PLACE")) c->lazy_ok = atoi(e) != 0;
+  if (dmalloc(&c->spill[0], (uint64_t)c->nregions * SHK_SPILL_STRIDE) || dmalloc(&c->d_over_list, (uint64_t)c->nregions + 1)) return SHK_ERR_HIP;
   { uint64_t nt = c->nregions / SHK_RSCAN_TILE + 2;
     if (dmalloc(&c->d_tile_a, nt) || dmalloc(&c->d_tile_b, nt) || dmalloc(&c->d_tile_f, nt)) return SHK_ERR_HIP; }
   if (dmalloc(&c->d_counters, SHK_NCOUNTERS)) return SHK_ERR_HIP;
@@ -367,7 +376,7 @@ extern "C" void shk_destroy(shk_ctx *c) {
   for (int i = 0; i < 2; i++) { hipFree(c->tab[i]); hipFree(c->fin[i]); hipFree(c->d_send[i]); }
   hipFree(c->d_isum); hipFree(c->d_ilens); hipFree(c->d_fin_i); hipFree(c->d_prot);
   hipFree(c->d_newchunks); hipFree(c->d_chist); hipHostFree(c->h_chist);
-  hipFree(c->d_spill); hipFree(c->d_over_list); hipFree(c->d_summary); hipFree(c->d_dump_offs); hipFree(c->d_tile_a); hipFree(c->d_tile_b); hipFree(c->d_tile_f); hipFree(c->d_counters);
+  hipFree(c->spill[0]); hipFree(c->spill[1]); hipFree(c->d_over_list); hipFree(c->d_summary); hipFree(c->d_dump_offs); hipFree(c->d_tile_a); hipFree(c->d_tile_b); hipFree(c->d_tile_f); hipFree(c->d_counters);
   bufs_free(c, c);
   delete c;
 }
@@ -687,11 +696,16 @@ static int partition_stage(const shk_ctx *c, ShkStageBufs *b, int src, uint64_t 
 #define SHK_FOR_REGION_SLICES(c, A, nblk) \
   for (uint32_t r0_ = 0, nblk = 0; r0_ < (c)->nregions && ((A).r0 = r0_, nblk = (c)->nregions - r0_ < SHK_REGION_SLICE ? (c)->nregions - r0_ : SHK_REGION_SLICE, true); r0_ += SHK_REGION_SLICE)
 
+// rec: the old side comes from the records (no image: the small instantiation serves both image sizes)
 template <int MODE>
-static void launch_merge(shk_ctx *c, const ShkMergeArgs &A0) {
+static void launch_merge(shk_ctx *c, const ShkMergeArgs &A0, bool rec = false) {
   ShkMergeArgs A = A0;
   SHK_FOR_REGION_SLICES(c, A, nblk) {
-    if (c->big_image)
+    // (the write pass, MODE 1, has no record-sourced form: naming MODE 0 in its place keeps launch_merge<1> from
+    // instantiating one that the test in front never lets run)
+    if (MODE != 1 && rec)
+      hipLaunchKernelGGL((k_region_merge<MODE == 1 ? 0 : MODE, SHK_IMG_BLOCKS, false, true>), dim3(nblk), dim3(c->merge_group), 0, c->stream, A);
+    else if (c->big_image)
       hipLaunchKernelGGL((k_region_merge<MODE, SHK_IMG_BLOCKS_BIG>), dim3(nblk), dim3(c->merge_group), 0, c->stream, A);
     else
       hipLaunchKernelGGL((k_region_merge<MODE, SHK_IMG_BLOCKS>), dim3(nblk), dim3(c->merge_group), 0, c->stream, A);
@@ -702,6 +716,44 @@ struct MergeOut {
   uint64_t newd, added, removed;
   uint32_t err;
 };
+
+// where a pass writes its records: never over the ones that describe the live table
+static uint8_t *spill_out(const shk_ctx *c) { return c->spill[c->rec_live ? c->live ^ 1 : c->live]; }
+
+// the second record buffer; without it the context places at every commit for the rest of its life (not an error)
+static bool lazy_reserve(shk_ctx *c) {
+  if (!c->lazy_ok || c->spill[1]) return c->lazy_ok != 0;
+  void *v = nullptr;
+  if (hipMalloc(&v, (uint64_t)c->nregions * SHK_SPILL_STRIDE + SHK_SLACK) != hipSuccess) {
+    (void)hipGetLastError();
+    c->lazy_ok = 0;
+    return false;
+  }
+  c->spill[1] = (uint8_t *)v;
+  return true;
+}
+
+static void fill_args(shk_ctx *c, ShkMergeArgs *A, const uint64_t *words, uint32_t lo, uint32_t hi, int denoise);
+// The live table's bytes, if a lazy commit left them unwritten: placement from the records and free pointers that
+// describe it. At the top of everything that reads c->tab[c->cur].
+static int table_sync(shk_ctx *c) {
+  if (!c->table_stale) return SHK_OK;
+  ShkMergeArgs A;
+  fill_args(c, &A, nullptr, 0, 0, 0);
+  A.tabB = c->tab[c->cur]; A.finB = c->fin[c->cur]; A.spill = c->spill[c->live]; A.summary = nullptr;
+  HIPCHK(hipMemsetAsync(c->tab[c->cur], 0, c->table_bytes, c->stream));
+  { ProfScope ps(c, KP_PLACE);
+    SHK_FOR_REGION_SLICES(c, A, nblk)
+      hipLaunchKernelGGL((k_region_place<SHK_IMG_BLOCKS>), dim3(nblk), dim3(SHK_WAVE), 0, c->stream, A); }
+  HIPCHK(hipGetLastError());
+  // The table counts as written only once the placement has run without raising an error bit: a reader behind a failed
+  // placement must fail again, not read half a table. (One wait per read of a stale table, not per batch.)
+  uint32_t bits = 0;
+  if (fetch_err(c, &bits)) return SHK_ERR_HIP;
+  if (bits) return map_err_bits(bits);
+  c->table_stale = 0;
+  return SHK_OK;
+}
 
 static void fill_args(shk_ctx *c, ShkMergeArgs *A, const uint64_t *words, uint32_t lo, uint32_t hi, int denoise) {
   A->want_hist = 0;
@@ -716,7 +768,7 @@ static void fill_args(shk_ctx *c, ShkMergeArgs *A, const uint64_t *words, uint32
 #endif
   { const char *sp = getenv("SHK_STAMPS");    // diagnostics: "fused" = only the one-pass deNoise launches, "plain" = all the others, else all
     A->dbg = (sp && strcmp(sp, "fused") != 0) ? (unsigned long long *)(c->d_scalars + 16) : nullptr; }
-  A->spill = c->d_spill; A->over_list = c->d_over_list; A->n_over = c->d_counters + SHK_CNT_NOVER; A->list = nullptr;
+  A->spill = spill_out(c); A->orec = c->spill[c->live]; A->over_list = c->d_over_list; A->n_over = c->d_counters + SHK_CNT_NOVER; A->list = nullptr;
   A->newchunks = nullptr; A->chist = nullptr;
   A->counted = c->counted;
   A->r0 = 0; A->rstride = 1;
@@ -737,6 +789,9 @@ static int ensure_chist(shk_ctx *c) {
 // spill: the summary keeps the runs for k_region_place (a write pass for the same request only places them)
 static int merge_summary(shk_ctx *c, const uint64_t *words, uint32_t lo, uint32_t hi, int denoise, MergeOut *o,
                          bool with_chist, bool spill) {
+  // (a deNoise round reads the traveled bits k_denoise_marks left in the table: its callers have synced it)
+  const bool rec = c->rec_live && !denoise;
+  if (!rec) { int rc = table_sync(c); if (rc) return rc; }
   ShkMergeArgs A;
   fill_args(c, &A, words, lo, hi, denoise);
   HIPCHK(hipMemsetAsync(c->d_counters, 0, (SHK_CNT_NOVER + 1) * 8, c->stream));
@@ -748,9 +803,9 @@ static int merge_summary(shk_ctx *c, const uint64_t *words, uint32_t lo, uint32_
     HIPCHK(hipMemsetAsync(c->d_chist, 0, SHK_MAX_CHUNKS * 8, c->stream));
   }
   if (spill) { ProfScope ps(c, KP_MERGE_SPILL);
-    launch_merge<3>(c, A); }
+    launch_merge<3>(c, A, rec); }
   else { ProfScope ps(c, KP_MERGE_SUM);
-    launch_merge<0>(c, A); }
+    launch_merge<0>(c, A, rec); }
   { ProfScope ps(c, KP_REGION_SCAN);
     const uint32_t ntiles = (c->nregions + SHK_RSCAN_TILE - 1) / SHK_RSCAN_TILE;
     hipLaunchKernelGGL(k_region_scan_a, dim3(ntiles), dim3(c->threads), 0, c->stream, c->d_summary, c->nregions, c->d_tile_a, c->d_tile_b);
@@ -780,12 +835,23 @@ static int merge_summary(shk_ctx *c, const uint64_t *words, uint32_t lo, uint32_
 }
 
 // write launch for the summary that was just computed; then flip the live table
+// (the commit point: lazily when the pass left a complete set of records -- nothing on the over list, small image, no
+// counted insert -- by making those records and its scan's free pointers the truth; otherwise the table is written now)
 static int merge_write(shk_ctx *c, const uint64_t *words, uint32_t lo, uint32_t hi, int denoise) {
+  const bool match = c->spill_valid && c->spill_words == words && c->spill_lo == lo && c->spill_hi == hi && c->spill_denoise == denoise &&
+                     c->spill_big == c->big_image;
+  if (match && c->spill_nover == 0 && !c->big_image && !c->counted && lazy_reserve(c)) {
+    if (c->rec_live) c->live ^= 1;
+    c->rec_live = 1; c->table_stale = 1;
+    c->spill_valid = 0;
+    c->cur ^= 1;
+    return SHK_OK;
+  }
+  if (!match || c->spill_nover) { int rc = table_sync(c); if (rc) return rc; }   // (the write pass reads table A)
   ShkMergeArgs A;
   fill_args(c, &A, words, lo, hi, denoise);
   HIPCHK(hipMemsetAsync(c->tab[c->cur ^ 1], 0, c->table_bytes, c->stream));
-  if (c->spill_valid && c->spill_words == words && c->spill_lo == lo && c->spill_hi == hi && c->spill_denoise == denoise &&
-      c->spill_big == c->big_image) {
+  if (match) {
     // the summary launch left lengths and encodings behind: placement only
     { ProfScope ps(c, KP_PLACE);
       SHK_FOR_REGION_SLICES(c, A, nblk) {
@@ -807,12 +873,14 @@ static int merge_write(shk_ctx *c, const uint64_t *words, uint32_t lo, uint32_t 
   }
   c->spill_valid = 0;
   HIPCHK(hipGetLastError());
+  c->rec_live = 0; c->table_stale = 0;
   c->cur ^= 1;
   return SHK_OK;
 }
 
 static int denoise_round_once(shk_ctx *c, uint64_t *removed) {
   uint64_t ml = c->cfg.min_denoise_len ? c->cfg.min_denoise_len : (1ULL << 20);
+  { int rc = table_sync(c); if (rc) return rc; }
   { ProfScope ps(c, KP_MARKS);
     hipLaunchKernelGGL(k_denoise_marks, dim3(1), dim3(64), 0, c->stream, c->tab[c->cur], c->nslots, c->xnslots, c->nblocks,
                        ml, (unsigned long long *)(c->d_scalars + 3)); }
@@ -834,6 +902,7 @@ static int denoise_round_once(shk_ctx *c, uint64_t *removed) {
 static int denoise_with_rest(shk_ctx *c, const uint64_t *words, uint32_t lo, uint32_t hi, shk_batch_stats *st, bool *done) {
   *done = false;
   uint64_t ml = c->cfg.min_denoise_len ? c->cfg.min_denoise_len : (1ULL << 20);
+  { int rc = table_sync(c); if (rc) return rc; }
   { ProfScope ps(c, KP_MARKS);
     hipLaunchKernelGGL(k_denoise_marks, dim3(1), dim3(64), 0, c->stream, c->tab[c->cur], c->nslots, c->xnslots, c->nblocks,
                        ml, (unsigned long long *)(c->d_scalars + 3)); }
@@ -928,8 +997,10 @@ static int point_try(shk_ctx *c, const uint64_t *words, uint32_t lo, uint32_t sp
   c->chist_n = 0;
   HIPCHK(hipMemsetAsync(c->d_counters, 0, SHK_NCOUNTERS * 8, c->stream));
   { ProfScope ps(c, KP_MERGE_FUSED);
-    SHK_FOR_REGION_SLICES(c, A, nblk)
-      hipLaunchKernelGGL((k_region_merge<3, SHK_IMG_BLOCKS, true>), dim3(nblk), dim3(c->merge_group), 0, c->stream, A); }
+    SHK_FOR_REGION_SLICES(c, A, nblk) {
+      if (c->rec_live) hipLaunchKernelGGL((k_region_merge<3, SHK_IMG_BLOCKS, true, true>), dim3(nblk), dim3(c->merge_group), 0, c->stream, A);
+      else hipLaunchKernelGGL((k_region_merge<3, SHK_IMG_BLOCKS, true>), dim3(nblk), dim3(c->merge_group), 0, c->stream, A);
+    } }
   point_scans(c, true, true, 0);
   if (with_chist) {
     ProfScope ps(c, KP_MISC);
@@ -987,8 +1058,9 @@ static int point_finish(shk_ctx *c, const uint64_t *words, uint32_t lo, uint32_t
     HIPCHK(hipMemsetAsync(c->d_counters, 0, SHK_NCOUNTERS * 8, c->stream));
     HIPCHK(hipMemcpyAsync(c->d_over_list, regs.data(), regs.size() * 4, hipMemcpyHostToDevice, c->stream));
     A.list = c->d_over_list; A.prot_list = c->d_prot; A.nprot = (uint32_t)nprot;
-    { ProfScope ps(c, KP_MISC);
-      hipLaunchKernelGGL((k_region_merge<3, SHK_IMG_BLOCKS, true>), dim3((uint32_t)regs.size()), dim3(c->merge_group), 0, c->stream, A); }
+    { ProfScope ps(c, KP_MISC);   // (the same old side as the first go: its records are untouched)
+      if (c->rec_live) hipLaunchKernelGGL((k_region_merge<3, SHK_IMG_BLOCKS, true, true>), dim3((uint32_t)regs.size()), dim3(c->merge_group), 0, c->stream, A);
+      else hipLaunchKernelGGL((k_region_merge<3, SHK_IMG_BLOCKS, true>), dim3((uint32_t)regs.size()), dim3(c->merge_group), 0, c->stream, A); }
     HIPCHK(hipStreamSynchronize(c->stream));   // (regs lives on this stack frame)
     point_scans(c, true, false, 0);
     int rc = point_read(c, po);
@@ -1093,7 +1165,8 @@ static int sample_pass(shk_ctx *c, const uint64_t *words, uint32_t lo, uint32_t 
     for (uint32_t r0 = 0; r0 < ns; r0 += SHK_REGION_SLICE) {
       A.r0 = r0;
       const uint32_t nblk = ns - r0 < SHK_REGION_SLICE ? ns - r0 : SHK_REGION_SLICE;
-      hipLaunchKernelGGL((k_region_merge<0, SHK_IMG_BLOCKS>), dim3(nblk), dim3(c->merge_group), 0, c->stream, A);
+      if (c->rec_live) hipLaunchKernelGGL((k_region_merge<0, SHK_IMG_BLOCKS, false, true>), dim3(nblk), dim3(c->merge_group), 0, c->stream, A);
+      else hipLaunchKernelGGL((k_region_merge<0, SHK_IMG_BLOCKS>), dim3(nblk), dim3(c->merge_group), 0, c->stream, A);
     }
     hipLaunchKernelGGL(k_chunk_hist, dim3((ns + SHK_CHIST_REGIONS - 1) / SHK_CHIST_REGIONS), dim3(256), 0, c->stream,
                        c->d_newchunks, c->d_summary, c->nregions, c->d_chist, stride); }
@@ -1416,6 +1489,7 @@ extern "C" int shk_prepare_reserve(shk_ctx *c) {
   if (!c || c->cfg.num_shards > 1) return SHK_ERR_ARG;
   HIPCHK(hipSetDevice(c->dev));
   if (!c->front) { int rc = front_init(c); if (rc) { front_destroy(c); return rc; } }
+  lazy_reserve(c);               // (the second record buffer, otherwise allocated by the first lazy commit)
   if (c->cfg.num_denoise) {      // (the records of a deNoise point, otherwise allocated by the first pass that needs them)
     int rc = ensure_chist(c);
     if (!rc) rc = point_alloc(c);
@@ -1644,6 +1718,7 @@ extern "C" int shk_route_reserve(shk_ctx *c) {
     if (!c->d_send[b] && dmalloc(&c->d_send[b], c->cfg.max_batch_keys + 1)) return SHK_ERR_HIP;
   // (and the records of a deNoise point: a shard's rounds are decided outside the context)
   { int rc = ensure_chist(c); if (!rc) rc = point_alloc(c); if (rc) return rc; }
+  lazy_reserve(c);               // (the second record buffer, otherwise allocated by the first lazy commit)
   return SHK_OK;
 }
 
@@ -1745,6 +1820,7 @@ extern "C" int shk_stage_try_denoise(shk_ctx *c, uint32_t lo, uint32_t hi, shk_s
   if (!c || !out || hi < lo || hi >= SHK_MAX_CHUNKS) return SHK_ERR_ARG;
   HIPCHK(hipSetDevice(c->dev));
   uint64_t ml = c->cfg.min_denoise_len ? c->cfg.min_denoise_len : (1ULL << 20);
+  { int rc = table_sync(c); if (rc) return rc; }
   { ProfScope ps(c, KP_MARKS);
     hipLaunchKernelGGL(k_denoise_marks, dim3(1), dim3(64), 0, c->stream, c->tab[c->cur], c->nslots, c->xnslots, c->nblocks,
                        ml, (unsigned long long *)(c->d_scalars + 3)); }
@@ -1849,7 +1925,8 @@ extern "C" int shk_denoise(shk_ctx *c, uint64_t *removed) {
   if (!c) return SHK_ERR_ARG;
   HIPCHK(hipSetDevice(c->dev));
   uint64_t r = 0;
-  int rc = denoise_round(c, &r);
+  int rc = table_sync(c);
+  if (!rc) rc = denoise_round(c, &r);
   if (!rc) c->rounds_done++;
   if (removed) *removed = r;
   return finish(c, rc);
@@ -1887,7 +1964,9 @@ extern "C" int shk_header(shk_ctx *c, uint8_t out[128]) {
 extern "C" int shk_export_blocks(shk_ctx *c, void *dst, uint64_t cap) {
   if (!c || !dst || cap < c->table_bytes) return SHK_ERR_ARG;
   HIPCHK(hipSetDevice(c->dev));
+  { int rc = table_sync(c); if (rc) return rc; }
   HIPCHK(hipMemcpyAsync(dst, c->tab[c->cur], c->table_bytes, hipMemcpyDeviceToHost, c->stream));
+  { uint32_t bits = 0; if (fetch_err(c, &bits)) return SHK_ERR_HIP; if (bits) return map_err_bits(bits); }
   HIPCHK(hipStreamSynchronize(c->stream));
   return SHK_OK;
 }
@@ -1897,7 +1976,8 @@ extern "C" int shk_export_blocks(shk_ctx *c, void *dst, uint64_t cap) {
 extern "C" int shk_table_ptr(shk_ctx *c, void **d_table, uint64_t *nbytes) {
   if (!c || !d_table || !nbytes) return SHK_ERR_ARG;
   HIPCHK(hipSetDevice(c->dev));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  { int rc = table_sync(c); if (rc) return rc; }
+  { uint32_t bits = 0; if (fetch_err(c, &bits)) return SHK_ERR_HIP; if (bits) return map_err_bits(bits); }   // (synchronises)
   *d_table = c->tab[c->cur]; *nbytes = c->table_bytes;
   return SHK_OK;
 }
@@ -1920,6 +2000,7 @@ extern "C" int shk_export_cqf(shk_ctx *c, const char *path) {
 extern "C" int shk_import_blocks(shk_ctx *c, const void *src, uint64_t nbytes, uint64_t nelts, uint64_t ndistinct) {
   if (!c || !src || nbytes != c->table_bytes) return SHK_ERR_ARG;
   HIPCHK(hipSetDevice(c->dev));
+  c->rec_live = 0; c->table_stale = 0; c->spill_valid = 0;   // (the table is the truth again)
   HIPCHK(hipMemcpyAsync(c->tab[c->cur], src, nbytes, hipMemcpyHostToDevice, c->stream));
   { ProfScope ps(c, KP_MISC);
     hipLaunchKernelGGL(k_build_fin, dim3(c->nregions / 256 + 1), dim3(256), 0, c->stream, c->tab[c->cur], c->nslots,
@@ -1950,6 +2031,7 @@ extern "C" int shk_lookup(shk_ctx *c, const uint64_t *keys, uint64_t n, int on_d
   if (!c || (n && (!keys || !counts)) || mode < 0 || mode > 2) return SHK_ERR_ARG;
   if (n == 0) return SHK_OK;
   HIPCHK(hipSetDevice(c->dev));
+  { int rc = table_sync(c); if (rc) return rc; }
   uint64_t *dk = nullptr, *dc = nullptr; uint8_t *dt = nullptr;
   if (on_device) { dk = (uint64_t *)keys; dc = counts; dt = was_traveled; }
   else {
@@ -1992,6 +2074,7 @@ extern "C" int shk_insert_counted(shk_ctx *c, const uint64_t *keys, const uint64
   if (stats) *stats = st;
   if (n == 0) return SHK_OK;
   HIPCHK(hipSetDevice(c->dev));
+  { int rc = table_sync(c); if (rc) return rc; }
   uint64_t *dk = nullptr, *dc = nullptr, *doff = nullptr;
   uint32_t *dnw = nullptr;
   int rc = SHK_OK;
@@ -2069,6 +2152,7 @@ extern "C" int shk_dump(shk_ctx *c, uint64_t *keys, uint64_t *counts, uint64_t c
                         uint64_t *n_out) {
   if (!c || !n_out || (keys && !counts)) return SHK_ERR_ARG;
   HIPCHK(hipSetDevice(c->dev));
+  { int rc = table_sync(c); if (rc) return rc; }
   ShkMergeArgs A;
   fill_args(c, &A, nullptr, 0, 0, 0);
   uint32_t *nper = c->d_over_list;                       // scratch of the spill scheme: [nregions + 1]
@@ -2124,6 +2208,7 @@ extern "C" int shk_dump(shk_ctx *c, uint64_t *keys, uint64_t *counts, uint64_t c
 static int merge2_run(shk_ctx *c, const ShkSrc2 &S, uint64_t *newd_out, uint64_t *added_out) {
   ShkMergeArgs A;
   uint64_t newd = 0, added = 0;
+  { int rc = table_sync(c); if (rc) return rc; }
   for (int attempt = 0; attempt < 2; attempt++) {
     fill_args(c, &A, nullptr, 0, 0, 0);
     HIPCHK(hipMemsetAsync(c->d_counters, 0, (SHK_CNT_NOVER + 1) * 8, c->stream));
@@ -2155,6 +2240,7 @@ static int merge2_run(shk_ctx *c, const ShkSrc2 &S, uint64_t *newd_out, uint64_t
       else hipLaunchKernelGGL((k_region_merge2<true, SHK_IMG_BLOCKS>), dim3(nblk), dim3(SHK_WAVE), 0, c->stream, A, S);
     } }
   HIPCHK(hipGetLastError());
+  c->rec_live = 0; c->table_stale = 0;
   c->cur ^= 1;
   *newd_out = newd; *added_out = added;
   return SHK_OK;
@@ -2165,6 +2251,7 @@ extern "C" int shk_merge(shk_ctx *dst, shk_ctx *src, shk_batch_stats *stats) {
   if (dst->dev != src->dev || dst->cfg.qb != src->cfg.qb || dst->cfg.hb != src->cfg.hb || dst->q_lo != src->q_lo || dst->nslots != src->nslots)
     return SHK_ERR_ARG;
   HIPCHK(hipSetDevice(dst->dev));
+  { int rc = table_sync(src); if (rc) return rc; }
   HIPCHK(hipStreamSynchronize(src->stream));   // the source's table must be at rest
   ShkSrc2 S;
   memset(&S, 0, sizeof(S));
@@ -2207,6 +2294,7 @@ extern "C" int shk_import_shards(shk_ctx *c, const void *const *shard_blocks, co
   for (uint32_t s = 0; s < nshards; s++) if (shard_bytes[s] != s_bytes || !shard_blocks[s]) return SHK_ERR_ARG;
   HIPCHK(hipSetDevice(c->dev));
   // start from an empty table
+  c->rec_live = 0; c->table_stale = 0; c->spill_valid = 0;
   HIPCHK(hipMemsetAsync(c->tab[c->cur], 0, c->table_bytes + SHK_SLACK, c->stream));
   HIPCHK(hipMemsetAsync(c->fin[c->cur], 0, ((uint64_t)c->nregions + 2) * 8, c->stream));
   c->nelts = 0; c->ndistinct = 0;
@@ -2246,6 +2334,7 @@ extern "C" int shk_select_seeds(shk_ctx *c, const void *text, int text_on_device
   if (!c || !text || !out_seeds || !out_counts || !n_out || nchunks == 0 || nchunks > SHK_MAX_CHUNKS) return SHK_ERR_ARG;
   if (k < 2 || k > SHK_WALK_MAX_K) return SHK_ERR_ARG;
   HIPCHK(hipSetDevice(c->dev));
+  { int rc = table_sync(c); if (rc) return rc; }
   const uint8_t *dtext;
   uint64_t nreads;
   if (upload_wait(c, text, text_on_device, c->stream)) return SHK_ERR_HIP;
@@ -2295,6 +2384,7 @@ extern "C" int shk_extend_forward(shk_ctx *c, const char *cur_kmers, const char 
   if (k < 2 || k > SHK_WALK_MAX_K || max_ext == 0) return SHK_ERR_ARG;
   if (n == 0) return SHK_OK;
   HIPCHK(hipSetDevice(c->dev));
+  { int rc_ = table_sync(c); if (rc_) return rc_; }
   // scratch of this call, released on every way out
   struct Scratch {
     char *dk = nullptr, *df = nullptr, *db = nullptr;
@@ -2487,6 +2577,7 @@ static int ug_reserve(shk_unitig_set *u, uint64_t ncontigs_after, uint64_t nlist
 }
 
 static int ug_bind(shk_unitig_set *u, shk_ctx *c, uint32_t k, uint64_t amin, uint32_t max_len) {
+  { int rc = table_sync(c); if (rc) return rc; }
   if (u->c) {
     if (u->c != c || u->k != k || u->amin != amin || u->max_len != max_len) return SHK_ERR_ARG;   // one filter, one set of rules
     return SHK_OK;
@@ -2518,6 +2609,7 @@ static int ug_bind(shk_unitig_set *u, shk_ctx *c, uint32_t k, uint64_t amin, uin
 // rounds of k_ug_walk until no contig is open; d_list[0] holds `nactive` ids
 static int ug_run(shk_unitig_set *u, uint32_t nactive, int mark) {
   shk_ctx *c = u->c;
+  { int rc = table_sync(c); if (rc) return rc; }
   // Extensions per contig and launch. A launch lasts as long as its longest walk while the neighbours that the short
   // ones queued wait for the next one: with many contigs open, short launches keep the frontier moving (2 M unitigs of a
   // 100x C. elegans graph, 126 M extensions: 1.25 s at 2048 steps per launch, 0.92 at 512, 0.56 at 128, 0.49 at 64, 0.47 at
@@ -2556,6 +2648,7 @@ extern "C" int shk_unitigs_add_seeds(shk_ctx *c, shk_unitig_set *u, const char *
   if (!c || !u || (n && (!seeds || !seed_counts))) return SHK_ERR_ARG;
   if (k < 2 || k > SHK_WALK_MAX_K || max_len < k + 1) return SHK_ERR_ARG;
   HIPCHK(hipSetDevice(c->dev));
+  { int rc_ = table_sync(c); if (rc_) return rc_; }
   int rc = ug_bind(u, c, k, abundance_min, max_len);
   if (rc || n == 0) return rc;
   if ((uint64_t)n > u->seeds_cap) {
@@ -2585,6 +2678,7 @@ extern "C" int shk_unitigs_add_reads(shk_ctx *c, shk_unitig_set *u, const void *
   if (!c || !u || !text || !chunk_off || !chunk_len || nchunks == 0 || nchunks > SHK_MAX_CHUNKS) return SHK_ERR_ARG;
   if (k < 2 || k > SHK_WALK_MAX_K || max_len < k + 1) return SHK_ERR_ARG;
   HIPCHK(hipSetDevice(c->dev));
+  { int rc_ = table_sync(c); if (rc_) return rc_; }
   int rc = ug_bind(u, c, k, abundance_min, max_len);
   if (rc) return rc;
   const uint8_t *dtext;
@@ -2647,6 +2741,7 @@ extern "C" int shk_unitig_set_write(shk_unitig_set *u, uint32_t k, const char *o
   if (k != u->k) { fclose(fo); return SHK_ERR_ARG; }
   shk_ctx *c = u->c;
   HIPCHK(hipSetDevice(c->dev));
+  { int rc_ = table_sync(c); if (rc_) return rc_; }
   const uint32_t n = u->ncontigs;
   uint32_t *d_keep = nullptr, *d_lens = nullptr, *d_ulen = nullptr, *d_ul1 = nullptr, *d_cnt = nullptr;
   uint64_t *d_newid = nullptr, *d_off = nullptr, *d_uoff = nullptr, *d_sums = nullptr;
@@ -2797,6 +2892,7 @@ extern "C" int shk_profile_reset(shk_ctx *c) {
 }
 extern "C" int shk_profile_get(shk_ctx *c, shk_kernel_time *out, int cap) {
   if (!c || !out) return SHK_ERR_ARG;
+  prof_collect(c);              // (a placement launched by a reader such as shk_export_blocks is still pending)
   int n = 0;
   for (int i = 0; i < KP_N && n < cap; i++) {
     out[n].name = kp_names[i]; out[n].launches = c->prof_n[i]; out[n].ms = c->prof_ms[i]; n++;
