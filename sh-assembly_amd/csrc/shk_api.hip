@@ -37,6 +37,55 @@ static const char *kp_names[KP_N] = {
 
 struct PendingEvent { int id; hipEvent_t a, b; };
 
+// The 64 words of ShkStageBufs::d_scalars. Kernels take pointers to them; an entry point runs alone on its context, so
+// slots of different owners are never in flight together.
+#define SHK_SCALAR_WORDS 64
+enum ShkDevSlot {
+  DS_NREADS = 0,       // parse_stage: reads of the batch (k_scan_chunks writes it; the key-count, hash, pack and roll kernels read it)
+  DS_NWORDS = 1,       // hash_stage, roll_stage, set_nwords: key words of the batch (the partition kernels read it)
+  DS_SCAN_TOTAL = 2,   // run_scan: total of the scan in flight
+  DS_MARKS = 3,        // k_denoise_marks, k_denoise_marks_virtual: singletons the range walk protects
+  DS_MAX_COUNT = 4,    // shk_insert_counted: largest count of the slice (k_expand_counted<0>)
+  DS_DUMP_STOP = 5,    // shk_dump: where the reference's iterator would end
+  DS_WALK_IN = 8,      // point_walk: state of the range walk entering this shard, 2 words
+  DS_WALK_OUT = 10,    // point_walk: ... and leaving it, 2 words
+  DS_STAMPS = 16,      // SHK_STAMPS diagnostics: 16 words of cycle counts (ShkMergeArgs::dbg)
+  DS_PAIR_LEN = 40,    // shk_stage_words_pair: lengths of the two sources, 2 words
+  DS_PAIR_BASE = 42,   // shk_stage_words_pair: their one-bucket base arrays {0, na} and {0, nb}, 2 + 2 words
+  DS_END = 46
+};
+// The 64 words of the pinned mirror ShkStageBufs::h_pinned: what the host reads back, and small uploads' sources.
+enum ShkHostSlot {
+  HP_COUNTERS = 0,     // merge_summary, point_read, merge2_run: d_counters, SHK_NCOUNTERS words (CNT_*, SHK_CNT_*)
+  HP_ERR = 40,         // err_enqueue / err_take: the error word (4 bytes)
+  HP_NREADS = 41,      // parse_stage: DS_NREADS read back
+  HP_NWORDS = 42,      // front_end, shk_hash_chunks: DS_NWORDS read back
+  HP_NWORDS_IN = 43,   // set_nwords: source of the upload to DS_NWORDS
+  HP_FREE_PTR = 44,    // shk_stats: free pointer behind the last region
+  HP_TOTAL = 45,       // shk_insert_counted: words of the slice; shk_dump: entries; unitig write: units
+  HP_AUX = 46,         // shk_insert_counted: DS_MAX_COUNT read back; shk_dump: DS_DUMP_STOP in and out; unitig write: total length
+  HP_MARKS = 47,       // point_walk: DS_MARKS read back
+  HP_IFIN = 48,        // point_try: free pointer behind the intermediate table's last region
+  HP_IFIRST = 49,      // point_try: first length byte of the intermediate table (quotient 0 has a run)
+  HP_WALK_IN = 50,     // point_walk: source of the upload to DS_WALK_IN, 2 words
+  HP_WALK_OUT = 52,    // point_walk: DS_WALK_OUT read back, 2 words
+  HP_PAIR = 56,        // shk_stage_words_pair: source of the upload to DS_PAIR_LEN and DS_PAIR_BASE, 6 words
+  HP_END = 62
+};
+enum { CNT_NEWD, CNT_ADDED, CNT_REMOVED, CNT_ADDED_BEFORE };   // counters[0..3]: the statistics of a pass (ShkMergeArgs::counters)
+static_assert(HP_COUNTERS + SHK_NCOUNTERS <= HP_ERR, "the counters mirror ends before the error word");
+static_assert(DS_END <= SHK_SCALAR_WORDS && HP_END <= SHK_SCALAR_WORDS, "both blocks fit their 64 words");
+static_assert(DS_PAIR_BASE + 4 == DS_END && HP_PAIR + (DS_END - DS_PAIR_LEN) == HP_END, "the pair block is uploaded in one copy");
+
+// How a partition level runs, fixed by the geometry (create_init); a batch adds what its producer has counted already
+// (ShkPartInput::counted) and whether region slots are worth trying (slot_capacity).
+enum { RP_SCATTER_GROUPED, RP_SCATTER_WIDE, RP_SCATTER_TILE };   // 16384-key windows with window groups; with PMAX 256; 4096-key windows
+struct ShkPartLevel {
+  uint8_t scatter;     // k_rp_scatter instantiation
+  bool pair_hist;      // when this level's words arrive unsorted, its counting pass also counts the next level (k_rp_hist2)
+  bool may_slot;       // the last level, of index >= 1, with 4-byte output: region slots instead of a counting pass
+};
+
 // What a front end (parse, hash or roll, partition) works in: its stream, every buffer it writes, the state of its
 // partition and the kernel times recorded on its stream. A context is one (the serial front end and everything behind
 // it run there); the overlapped front end owns a second (ShkFront). The stage functions take the context for geometry and
@@ -51,7 +100,7 @@ struct ShkStageBufs {
   uint32_t *d_nkeys = nullptr;
   uint64_t *d_key_base = nullptr;
   uint64_t *d_words[2] = {};
-  uint64_t *d_scalars = nullptr;          // [0] nreads, [1] nwords, [2] scan total scratch, [3] marks
+  uint64_t *d_scalars = nullptr;          // [SHK_SCALAR_WORDS], see ShkDevSlot
   uint64_t *d_block_sums = nullptr;
   uint64_t *d_hist[4] = {};               // per level: nbuckets*P (first level: times its window groups)
   uint64_t *d_base_sub = nullptr;         // first level with window groups: scanned bases of the (digit, group) sub-buckets
@@ -59,14 +108,12 @@ struct ShkStageBufs {
   uint64_t *d_cursor = nullptr;
   uint32_t *d_tfb = nullptr;
   uint32_t *d_err = nullptr;
-  uint64_t *h_pinned = nullptr;           // pinned mirror: counters [0, SHK_NCOUNTERS), err [40], scalars [41, 64)
+  uint64_t *h_pinned = nullptr;           // [SHK_SCALAR_WORDS] pinned, see ShkHostSlot
   uint32_t last_err_bits = 0;
   uint32_t region_cap = 0;      // how the partitioned words lie: 0 = d_base[nlevels] holds exact offsets; else region r owns the slot
                                 // [r * region_cap, ...) and d_base[nlevels][r] is its END (ShkRpLevel::slot_cap)
   uint32_t slot_overflows = 0;  // consecutive batches whose slotted last level overflowed; at 2 the slots are switched off
   int slots_off = 0;
-  const uint64_t *stage2_b = nullptr;     // shk_stage_words_pair: the second source of the first partition level (null = one source)
-  uint64_t stage2_na = 0, stage2_nb = 0;
   // profiling
   double prof_ms[KP_N] = {};
   uint64_t prof_n[KP_N] = {};
@@ -83,6 +130,8 @@ struct shk_ctx : ShkStageBufs {
   uint32_t nregions, rbits;     // regions and ceil(log2(nregions))
   uint32_t nlevels;
   ShkRpLevel lv[4];
+  ShkPartLevel part[4];         // the partition plan, level by level
+  bool roll_two;                // roll_stage's histogram pass counts the first two levels' digits together (they fit its LDS bins)
   uint32_t threads, hash_groups;
   // state
   uint64_t nelts, ndistinct;
@@ -99,7 +148,6 @@ struct shk_ctx : ShkStageBufs {
   long long *d_tile_a, *d_tile_b, *d_tile_f;
   uint64_t *d_dump_offs;        // [nregions + 2] shk_dump: where every region's entries start in the output
   int big_image;                // 1: rebuild kernels run with the SHK_IMG_BLOCKS_BIG image (set after a cluster outgrew the small one)
-  uint32_t merge_group;         // threads per region workgroup (one wave rebuilds; the others help staging and folding)
   // the summary launch spills lengths + encodings per region, k_region_place writes table B from them
   // Lazy placement: a clean pass is committed by keeping its records (and the free pointers of its scan) as the truth;
   // the next pass reads them as its old side (the OLDREC instantiations of k_region_merge) and writes the other buffer;
@@ -207,7 +255,6 @@ static int bufs_alloc(const shk_ctx *c, ShkStageBufs *b, bool lent) {
   const uint64_t capk = c->cfg.max_batch_keys;
   const uint32_t maxch = SHK_MAX_CHUNKS;
   b->lent = lent;
-  b->slots_off = getenv("SHK_NO_SLOTS") ? 1 : 0;
   // (a higher stream priority changes nothing measurable: the rebuild's small workgroups refill every CU as fast as they
   // leave it, whatever the priority of the queue whose big workgroups are waiting)
   if (lent) HIPCHK(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
@@ -218,8 +265,8 @@ static int bufs_alloc(const shk_ctx *c, ShkStageBufs *b, bool lent) {
   if (dmalloc(&b->d_rd_start, c->max_reads + 1) || dmalloc(&b->d_rd_end, c->max_reads + 1) ||
       dmalloc(&b->d_nkeys, c->max_reads + 1) || dmalloc(&b->d_rd_chunk, c->max_reads + 1) || dmalloc(&b->d_key_base, c->max_reads + 2)) return SHK_ERR_HIP;
   if (!lent && (dmalloc(&b->d_words[0], capk + 1) || dmalloc(&b->d_words[1], capk + 1))) return SHK_ERR_HIP;
-  if (dmalloc(&b->d_scalars, 64)) return SHK_ERR_HIP;
-  HIPCHK(hipMemsetAsync(b->d_scalars, 0, 64 * 8, b->stream));
+  if (dmalloc(&b->d_scalars, SHK_SCALAR_WORDS)) return SHK_ERR_HIP;
+  HIPCHK(hipMemsetAsync(b->d_scalars, 0, SHK_SCALAR_WORDS * 8, b->stream));
   {
     uint64_t mx = capk > c->max_reads ? capk : c->max_reads;
     uint64_t pw = 1ULL << c->rbits;
@@ -238,7 +285,7 @@ static int bufs_alloc(const shk_ctx *c, ShkStageBufs *b, bool lent) {
   if (dmalloc(&b->d_tfb, capk / SHK_RP_TILE + 2)) return SHK_ERR_HIP;
   if (dmalloc(&b->d_err, 4)) return SHK_ERR_HIP;
   HIPCHK(hipMemsetAsync(b->d_err, 0, 16, b->stream));
-  HIPCHK(hipHostMalloc((void **)&b->h_pinned, 64 * sizeof(uint64_t), hipHostMallocDefault));
+  HIPCHK(hipHostMalloc((void **)&b->h_pinned, SHK_SCALAR_WORDS * sizeof(uint64_t), hipHostMallocDefault));
   HIPCHK(hipStreamSynchronize(b->stream));
   return SHK_OK;
 }
@@ -298,6 +345,16 @@ static int create_init(shk_ctx *c, const shk_config *cfg) {
   c->threads = cfg->threads_per_group ? cfg->threads_per_group : 512;
   if (c->threads < 64 || c->threads > 1024 || (c->threads & (c->threads - 1))) return SHK_ERR_ARG;
   c->hash_groups = cfg->hash_groups ? cfg->hash_groups : 2048;
+  // the partition plan
+  c->roll_two = c->nlevels >= 2 && c->lv[0].bits + c->lv[1].bits <= 14;   // two levels' digits fit one pass's LDS bins
+  for (uint32_t l = 0; l < c->nlevels; l++) {
+    const bool last = l + 1 == c->nlevels;
+    // a level in the middle: 16384-key windows as at the first level (digit runs of 1 KB instead of 256 bytes: 2.85 ->
+    // 2.25 ms per 832 M keys). Not the last level: its 4-byte records in slots gain nothing (3.4 ms either way)
+    c->part[l].scatter = l == 0 && c->lv[0].ng_log2 ? RP_SCATTER_GROUPED : c->threads >= 512 && !last && c->lv[l].bits <= 8 ? RP_SCATTER_WIDE : RP_SCATTER_TILE;
+    c->part[l].pair_hist = l == 0 && c->roll_two && c->lv[1].ng_log2 == 0;
+    c->part[l].may_slot = last && l >= 1 && c->lv[l].out32;
+  }
   c->rounds_left = cfg->num_denoise;
   c->max_reads = cfg->max_batch_reads ? cfg->max_batch_reads : cfg->max_batch_bytes / 16 + 1024;
   { int rc = bufs_alloc(c, c, false); if (rc) return rc; }
@@ -307,8 +364,6 @@ static int create_init(shk_ctx *c, const shk_config *cfg) {
   }
   if (dmalloc(&c->d_summary, SHK_SUM_STRIDE * (uint64_t)c->nregions + 8)) return SHK_ERR_HIP;
   if (dmalloc(&c->d_dump_offs, (uint64_t)c->nregions + 2)) return SHK_ERR_HIP;
-  c->merge_group = SHK_MERGE_GROUP;
-  if (const char *mg = getenv("SHK_MERGE_GROUP")) { int v = atoi(mg); if (v == 64 || v == 128) c->merge_group = (uint32_t)v; }
   // the sampled location of a deNoise point needs enough regions for the sample to mean something:
   // every 8th region; every 16th from 2^20 regions on (qb >= 28): a wrong guess costs one more one-pass point (18 ms at
   // qb 29), the sample 1.9 / 1.15 / 0.75 ms at stride 8 / 16 / 32; measured on the 12 points of the qb-29 bench: no wrong
@@ -333,7 +388,7 @@ static int create_init(shk_ctx *c, const shk_config *cfg) {
   if (cfg->num_denoise > 0 || cfg->num_shards > 1) {
     if (ensure_chist(c) || point_alloc(c)) return SHK_ERR_HIP;
   }
-  if (cfg->num_shards > 1 && !getenv("SHK_ROUTE_SINGLE_BUFFER")) {     // the two send buffers of shk_route_words, for the same reason
+  if (cfg->num_shards > 1) {     // the two send buffers of shk_route_words, for the same reason
     for (int b = 0; b < 2; b++)
       if (dmalloc(&c->d_send[b], c->cfg.max_batch_keys + 1)) return SHK_ERR_HIP;
   }
@@ -368,7 +423,7 @@ extern "C" void shk_destroy(shk_ctx *c) {
   }
   if (getenv("SHK_STAMPS") && c->d_scalars) {
     unsigned long long st[16];
-    hipMemcpy(st, c->d_scalars + 16, sizeof(st), hipMemcpyDeviceToHost);
+    hipMemcpy(st, c->d_scalars + DS_STAMPS, sizeof(st), hipMemcpyDeviceToHost);
     static const char *nm[9] = {"stage+init", "fold keys", "old rank/select", "count sort", "merge pass", "scan+stats", "(unused)", "placement", "stores"};
     unsigned long long tot = 0; for (int i = 0; i < 9; i++) tot += st[i];
     for (int i = 0; i < 9; i++) fprintf(stderr, "SHK_STAMPS %-16s %6.2f %%\n", nm[i], tot ? 100.0 * st[i] / tot : 0.0);
@@ -390,19 +445,31 @@ static int run_scan(const shk_ctx *c, ShkStageBufs *b, const T *in, uint64_t n_m
   if (!sums) sums = b->d_block_sums;
   const uint32_t nb = (uint32_t)(n_max / SHK_SCAN_TILE + 1);
   hipLaunchKernelGGL((k_scan_reduce<T>), dim3(nb), dim3(c->threads), 0, b->stream, in, n_max, n_dev, sums);
-  hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(c->threads), 0, b->stream, sums, (uint64_t)nb, b->d_scalars + 2);
+  hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(c->threads), 0, b->stream, sums, (uint64_t)nb, b->d_scalars + DS_SCAN_TOTAL);
   hipLaunchKernelGGL((k_scan_apply<T>), dim3(nb), dim3(c->threads), 0, b->stream, in, n_max, n_dev, sums,
-                     b->d_scalars + 2, out);
+                     b->d_scalars + DS_SCAN_TOTAL, out);
   HIPCHK(hipGetLastError());
   return 0;
 }
 
+// The error word's read-back in two halves, around the caller's synchronisation. err_take clears the device's word when
+// it is set; record: the bits also become last_err_bits (what the big-image retries look at).
+static int err_enqueue(ShkStageBufs *b) { HIPCHK(hipMemcpyAsync(b->h_pinned + HP_ERR, b->d_err, 4, hipMemcpyDeviceToHost, b->stream)); return 0; }
+static int err_take(ShkStageBufs *b, bool record, uint32_t *bits) {
+  *bits = *(uint32_t *)(b->h_pinned + HP_ERR);
+  if (*bits && record) b->last_err_bits = *bits;
+  if (*bits) HIPCHK(hipMemsetAsync(b->d_err, 0, 16, b->stream));
+  return 0;
+}
 static int fetch_err(ShkStageBufs *b, uint32_t *bits) {
-  HIPCHK(hipMemcpyAsync(b->h_pinned + 40, b->d_err, 4, hipMemcpyDeviceToHost, b->stream));
+  if (err_enqueue(b)) return SHK_ERR_HIP;
   HIPCHK(hipStreamSynchronize(b->stream));
-  *bits = *(uint32_t *)(b->h_pinned + 40);
-  if (*bits) b->last_err_bits = *bits;
-  if (*bits) hipMemsetAsync(b->d_err, 0, 16, b->stream);
+  return err_take(b, true, bits);
+}
+// the number of key words of the batch, where the partition kernels read it
+static int set_nwords(ShkStageBufs *b, uint64_t n) {
+  b->h_pinned[HP_NWORDS_IN] = n;
+  HIPCHK(hipMemcpyAsync(b->d_scalars + DS_NWORDS, b->h_pinned + HP_NWORDS_IN, 8, hipMemcpyHostToDevice, b->stream));
   return 0;
 }
 
@@ -440,11 +507,11 @@ static int parse_stage(const shk_ctx *c, ShkStageBufs *b, const void *text, int 
   { ProfScope ps(c, b, KP_COUNT_LINES);
     hipLaunchKernelGGL(k_count_lines, dim3(nchunks * SHK_PARSE_SEGS), dim3(c->threads), 0, b->stream, dtext, b->d_chunk_off, b->d_chunk_len, b->d_nlines); }
   { ProfScope ps(c, b, KP_SCAN_CHUNKS);
-    hipLaunchKernelGGL(k_scan_chunks, dim3(1), dim3(c->threads), 0, b->stream, b->d_nlines, nchunks, b->d_reads_base, b->d_scalars + 0); }
+    hipLaunchKernelGGL(k_scan_chunks, dim3(1), dim3(c->threads), 0, b->stream, b->d_nlines, nchunks, b->d_reads_base, b->d_scalars + DS_NREADS); }
   // the read arrays are sized by max_reads: the count is checked on the host below
-  HIPCHK(hipMemcpyAsync(b->h_pinned + 41, b->d_scalars, 8, hipMemcpyDeviceToHost, b->stream));
+  HIPCHK(hipMemcpyAsync(b->h_pinned + HP_NREADS, b->d_scalars + DS_NREADS, 8, hipMemcpyDeviceToHost, b->stream));
   HIPCHK(hipStreamSynchronize(b->stream));
-  const uint64_t nreads = b->h_pinned[41];
+  const uint64_t nreads = b->h_pinned[HP_NREADS];
   if (nreads > c->max_reads) return SHK_ERR_BATCH;
   { ProfScope ps(c, b, KP_EMIT_READS);
     hipLaunchKernelGGL(k_emit_reads, dim3(nchunks * SHK_PARSE_SEGS), dim3(c->threads), 0, b->stream, dtext, b->d_chunk_off, b->d_chunk_len,
@@ -454,7 +521,7 @@ static int parse_stage(const shk_ctx *c, ShkStageBufs *b, const void *text, int 
   return SHK_OK;
 }
 
-// text + chunk table -> key words in d_words[0]; d_scalars[1] = #words
+// text + chunk table -> key words in d_words[0]; d_scalars[DS_NWORDS] = #words
 static int hash_stage(const shk_ctx *c, ShkStageBufs *b, const void *text, int on_device, uint64_t text_bytes, const uint64_t *chunk_off,
                       const uint64_t *chunk_len, uint32_t nchunks, uint32_t chunk_first, uint32_t chunk_mul, bool hist0 = false) {
   // chunk i of this call is labelled chunk_first + i * chunk_mul; hist0: the hash kernel also fills the first partition
@@ -470,14 +537,13 @@ static int hash_stage(const shk_ctx *c, ShkStageBufs *b, const void *text, int o
   { ProfScope ps(c, b, KP_COUNT_KEYS);       // (one thread per read)
     const uint64_t blocks = nreads / 256 + 1;
     hipLaunchKernelGGL(k_count_keys, dim3((uint32_t)(blocks < (1u << 20) ? blocks : (1u << 20))), dim3(256), 0, b->stream, dtext, b->d_rd_start, b->d_rd_end,
-                       b->d_scalars + 0, c->cfg.k, b->d_nkeys, b->d_err); }
+                       b->d_scalars + DS_NREADS, c->cfg.k, b->d_nkeys, b->d_err); }
   if (run_scan<uint32_t>(c, b, b->d_nkeys, nreads, nullptr, b->d_key_base)) return SHK_ERR_HIP;
-  // total = key_base[nreads] -> d_scalars[1]
-  HIPCHK(hipMemcpyAsync(b->d_scalars + 1, b->d_key_base + nreads, 8, hipMemcpyDeviceToDevice, b->stream));
+  HIPCHK(hipMemcpyAsync(b->d_scalars + DS_NWORDS, b->d_key_base + nreads, 8, hipMemcpyDeviceToDevice, b->stream));
   { ProfScope ps(c, b, KP_HASH);
     const uint32_t ht = c->threads < SHK_HASH_WAVES * SHK_WAVE ? c->threads : SHK_HASH_WAVES * SHK_WAVE;
     hipLaunchKernelGGL(k_hash_reads, dim3(groups * (c->threads / ht)), dim3(ht), 0, b->stream, dtext, b->d_rd_start, b->d_rd_end,
-                       b->d_scalars + 0, b->d_rd_chunk, chunk_first, chunk_mul, b->d_key_base, c->cfg.k, c->cfg.hb,
+                       b->d_scalars + DS_NREADS, b->d_rd_chunk, chunk_first, chunk_mul, b->d_key_base, c->cfg.k, c->cfg.hb,
                        b->d_words[0], c->cfg.max_batch_keys, b->d_err, hist0 ? b->d_hist[0] : nullptr, c->lv[0].shift, c->lv[0].bits, c->q_lo, c->lv[0].ng_log2); }
   HIPCHK(hipGetLastError());
   return SHK_OK;
@@ -496,11 +562,11 @@ static int pack_stage(const shk_ctx *c, ShkStageBufs *b, ShkRollArgs &A, uint64_
   const uint32_t t = c->threads < 256 ? c->threads : 256;
   { const uint64_t blocks = nreads / t + 1;
     hipLaunchKernelGGL(k_pack_count, dim3((uint32_t)(blocks < 4096 ? blocks : 4096)), dim3(t), 0, b->stream, (const uint64_t *)b->d_rd_start,
-                       (const uint64_t *)b->d_rd_end, (const uint64_t *)(b->d_scalars + 0), c->cfg.k, b->d_nkeys); }
+                       (const uint64_t *)b->d_rd_end, (const uint64_t *)(b->d_scalars + DS_NREADS), c->cfg.k, b->d_nkeys); }
   if (run_scan<uint32_t>(c, b, b->d_nkeys, nreads, nullptr, b->d_key_base)) return SHK_ERR_HIP;
   { const uint64_t blocks = nreads * 4 / t + 1;
     hipLaunchKernelGGL(k_pack_reads, dim3((uint32_t)(blocks < 16384 ? blocks : 16384)), dim3(t), 0, b->stream, A.text, A.safe_end,
-                       (const uint64_t *)b->d_rd_start, (const uint64_t *)b->d_rd_end, (const uint64_t *)(b->d_scalars + 0),
+                       (const uint64_t *)b->d_rd_start, (const uint64_t *)b->d_rd_end, (const uint64_t *)(b->d_scalars + DS_NREADS),
                        (const uint64_t *)b->d_key_base, b->d_nkeys, (ShkQuad *)buf, cap_units); }
   A.pk = (const ShkQuad *)buf; A.pk_base = b->d_key_base; A.pk_flag = b->d_nkeys;
   return SHK_OK;
@@ -511,7 +577,7 @@ static int pack_stage(const shk_ctx *c, ShkStageBufs *b, ShkRollArgs &A, uint64_
 static void roll_args(const shk_ctx *c, ShkStageBufs *b, ShkRollArgs &A, const uint8_t *dtext, uint64_t text_bytes,
                       uint32_t chunk_first, uint32_t chunk_mul) {
   A.text = dtext; A.safe_end = (text_bytes + 15) & ~15ULL;
-  A.rd_start = b->d_rd_start; A.rd_end = b->d_rd_end; A.nreads_p = b->d_scalars + 0; A.rd_chunk = b->d_rd_chunk;
+  A.rd_start = b->d_rd_start; A.rd_end = b->d_rd_end; A.nreads_p = b->d_scalars + DS_NREADS; A.rd_chunk = b->d_rd_chunk;
   A.chunk_first = chunk_first; A.chunk_mul = chunk_mul; A.k = c->cfg.k; A.hb = c->cfg.hb;
   A.cap = c->cfg.max_batch_keys; A.err = b->d_err;
 }
@@ -538,10 +604,13 @@ static void launch_roll_scatter(const shk_ctx *c, ShkStageBufs *b, const ShkRoll
 }
 
 // text + chunk table -> key words in d_words[0], partitioned by the first region digit; d_base[1] = bucket bases,
-// d_scalars[1] = #words (roll_kernels.hip). For contexts with at least two partition levels.
-static bool roll_path(const shk_ctx *c) { return c->nlevels >= 2 && (c->q_lo & (SHK_REGION - 1)) == 0 && !getenv("SHK_NO_ROLL"); }
+// d_scalars[DS_NWORDS] = #words (roll_kernels.hip). For contexts with at least two partition levels; whether the histogram
+// pass has counted the second level too is the plan's roll_two.
+// (the roll kernels take q_lo as a multiple of 256: q_lo = nslots * shard_index with nslots a power of two, so any other
+// q_lo needs nslots < 256, which is one region and one level)
+static bool roll_path(const shk_ctx *c) { return c->nlevels >= 2; }
 static int roll_stage(const shk_ctx *c, ShkStageBufs *b, const void *text, int on_device, uint64_t text_bytes, const uint64_t *chunk_off,
-                      const uint64_t *chunk_len, uint32_t nchunks, uint32_t chunk_first, uint32_t chunk_mul, bool *level1_hist_ready) {
+                      const uint64_t *chunk_len, uint32_t nchunks, uint32_t chunk_first, uint32_t chunk_mul) {
   if (!chunk_labels_ok(nchunks, chunk_first, chunk_mul)) return SHK_ERR_BATCH;
   const uint8_t *dtext;
   uint64_t nreads;
@@ -549,8 +618,7 @@ static int roll_stage(const shk_ctx *c, ShkStageBufs *b, const void *text, int o
   const uint64_t P = 1ULL << c->lv[0].bits;
   // the first two levels' digits together, when they fit the histogram pass's LDS bins
   const uint32_t cb = c->lv[0].bits + c->lv[1].bits;
-  const bool two = cb <= 14 && !getenv("SHK_ROLL_HIST1");
-  *level1_hist_ready = two;
+  const bool two = c->roll_two;
   if (two) HIPCHK(hipMemsetAsync(b->d_hist[1], 0, (1ULL << cb) * 8, b->stream));
   else HIPCHK(hipMemsetAsync(b->d_hist[0], 0, P * 8, b->stream));
   ShkRollArgs A;
@@ -566,54 +634,65 @@ static int roll_stage(const shk_ctx *c, ShkStageBufs *b, const void *text, int o
                                 1u << c->lv[1].bits, b->d_hist[0]); }
   // bucket bases = exclusive scan of the digit counts; its total is the number of key words
   if (run_scan<uint64_t>(c, b, b->d_hist[0], P, nullptr, b->d_base[1])) return SHK_ERR_HIP;
-  HIPCHK(hipMemcpyAsync(b->d_scalars + 1, b->d_base[1] + P, 8, hipMemcpyDeviceToDevice, b->stream));
+  HIPCHK(hipMemcpyAsync(b->d_scalars + DS_NWORDS, b->d_base[1] + P, 8, hipMemcpyDeviceToDevice, b->stream));
   HIPCHK(hipMemcpyAsync(b->d_cursor, b->d_base[1], P * 8, hipMemcpyDeviceToDevice, b->stream));
   launch_roll_scatter(c, b, A, nreads);
   HIPCHK(hipGetLastError());
   return SHK_OK;
 }
 
-// words in d_words[src] (count in d_scalars[1], bound nmax) -> sorted by region in
-// d_words[*dst]; region offsets in d_base[nlevels]
-// (ext != null: the first level reads the caller's buffer instead of d_words[src])
-// first_level = 1: the words in d_words[src] are partitioned by the first digit already and d_base[1] holds the bucket
-// bases (roll_stage)
-static int partition_stage(const shk_ctx *c, ShkStageBufs *b, int src, uint64_t nmax, int *dst, const uint64_t *ext = nullptr, bool hist0_ready = false,
-                           uint32_t first_level = 0, bool hist1_ready = false) {
-  const uint64_t *n_p = b->d_scalars + 1;
+// What partition_stage reads (the number of words is in d_scalars[DS_NWORDS] as well), and its three producers
+struct ShkPartInput {
+  const uint64_t *src[2]; uint64_t n[2]; int nsrc;   // one or two sources of words (two: the first level reads both)
+  int in_buf;            // which d_words[] src[0] occupies; -1: neither
+  uint32_t first_level;  // 1: src[0] is partitioned by the first digit already and d_base[1] holds the bucket bases
+  bool counted[2];       // counted[l]: the producer has filled d_hist[l]
+};
+// roll_stage: d_words[0] sorted by the first digit; the second level is counted when the two levels' digits fit one pass
+static ShkPartInput part_from_roll(const shk_ctx *c, const ShkStageBufs *b, uint64_t n) { return {{b->d_words[0], nullptr}, {n, 0}, 1, 0, 1, {false, c->roll_two}}; }
+// hash_stage with hist0: d_words[0] in emission order, the first level counted
+static ShkPartInput part_from_hash(const ShkStageBufs *b, uint64_t n) { return {{b->d_words[0], nullptr}, {n, 0}, 1, 0, 0, {true, false}}; }
+// the caller's words, read in place (no staging copy), in one of the context's own buffers or not. w2: a second source
+// (shk_stage_words_pair: both are counted into one histogram and scattered with one set of cursors)
+static ShkPartInput part_from_words(const ShkStageBufs *b, const uint64_t *w, uint64_t n, const uint64_t *w2 = nullptr, uint64_t n2 = 0) {
+  return {{w, w2}, {n, n2}, w2 ? 2 : 1, w == b->d_words[0] ? 0 : w == b->d_words[1] ? 1 : -1, 0, {false, false}};
+}
+
+// Last level: fixed-capacity region slots instead of a histogram pass over the keys + scan, when the output buffer
+// (max_batch_keys 8-byte words = twice as many 4-byte records) gives every region room for its mean share of this
+// batch plus six sigma of a clumpy hash distribution (a true k-mer comes ~8 times per batch). A region that gets
+// more (repeats: one k-mer a million times) raises SHK_E_SLOT_FULL and the level is redone the exact way; after two
+// such batches in a row the context stops trying. 0: no slots for this batch.
+static uint32_t slot_capacity(const shk_ctx *c, uint64_t nregions, uint64_t nwords) {
+  uint64_t cp = 2 * c->cfg.max_batch_keys / nregions;
+  if (cp > (1u << 20)) cp = 1u << 20;
+  const double mean = (double)nwords / (double)nregions;
+  return cp >= 64 && (double)cp >= mean + 6.0 * sqrt(8.0 * mean + 1.0) + 16.0 ? (uint32_t)cp : 0;
+}
+
+// the words of `in` -> sorted by region in d_words[*dst]; region offsets in d_base[nlevels] (ShkStageBufs::region_cap)
+static int partition_stage(const shk_ctx *c, ShkStageBufs *b, const ShkPartInput &in, int *dst) {
+  const uint64_t *n_p = b->d_scalars + DS_NWORDS;
+  const uint64_t nmax = in.n[0] + in.n[1];
   { ProfScope ps(c, b, KP_RP_PREP);
     hipLaunchKernelGGL(k_rp_base1, dim3(1), dim3(64), 0, b->stream, n_p, b->d_base[0]); }
   const uint32_t nwin = (uint32_t)(nmax / SHK_RP_TILE + 1);
-  const uint64_t *in = ext ? ext : b->d_words[src];
-  int cur = ext ? 1 : src;   // the buffer `in` occupies (an external source leaves both free: write to d_words[0] first)
+  int cur = in.in_buf < 0 ? 1 : in.in_buf;   // the buffer the level's input occupies (neither: write to d_words[0] first)
+  bool counted[4] = {in.counted[0], in.counted[1], false, false};
   b->region_cap = 0;
-  // shk_stage_words_pair: the first level reads TWO buffers (the words a shard kept for itself, where the routing left them,
-  // and the words it received): both are counted into one histogram and scattered with one set of cursors. Their
-  // lengths and one-bucket base arrays live in d_scalars[40..45].
-  const uint64_t *in2 = (ext && first_level == 0) ? b->stage2_b : nullptr;
-  const uint64_t n_a = in2 ? b->stage2_na : nmax, n_b = in2 ? b->stage2_nb : 0;
-  for (uint32_t l = first_level; l < c->nlevels; l++) {
+  for (uint32_t l = in.first_level; l < c->nlevels; l++) {
+    const ShkPartLevel &pl = c->part[l];
     const uint64_t nb = c->lv[l].nbuckets, P = 1ULL << c->lv[l].bits;
     // the sources of this level: (words, their number on the device, their bucket bases, their number on the host)
-    struct Src { const uint64_t *w, *n_p, *base; uint64_t n; } srcs[2] = {{in, n_p, b->d_base[l], nmax}, {nullptr, nullptr, nullptr, 0}};
+    struct Src { const uint64_t *w, *n_p, *base; uint64_t n; } srcs[2] = {{l == in.first_level ? in.src[0] : b->d_words[cur], n_p, b->d_base[l], nmax}, {}};
     int nsrc = 1;
-    if (l == 0 && in2) {
-      srcs[0] = {in, b->d_scalars + 40, b->d_scalars + 42, n_a};
-      srcs[1] = {in2, b->d_scalars + 41, b->d_scalars + 44, n_b};
+    if (l == 0 && in.nsrc == 2) {
+      srcs[0] = {in.src[0], b->d_scalars + DS_PAIR_LEN, b->d_scalars + DS_PAIR_BASE, in.n[0]};
+      srcs[1] = {in.src[1], b->d_scalars + DS_PAIR_LEN + 1, b->d_scalars + DS_PAIR_BASE + 2, in.n[1]};
       nsrc = 2;
     }
-    // Last level: fixed-capacity region slots instead of a histogram pass over the keys + scan, when the output buffer
-    // (max_batch_keys 8-byte words = twice as many 4-byte records) gives every region room for its mean share of this
-    // batch plus six sigma of a clumpy hash distribution (a true k-mer comes ~8 times per batch). A region that gets
-    // more (repeats: one k-mer a million times) raises SHK_E_SLOT_FULL and the level is redone the exact way; after two
-    // such batches in a row the context stops trying.
-    uint32_t cap = 0;
-    if (l + 1 == c->nlevels && l >= 1 && c->lv[l].out32 && !b->slots_off && !(l == 1 && hist1_ready)) {
-      uint64_t cp = 2 * c->cfg.max_batch_keys / (nb * P);
-      if (cp > (1u << 20)) cp = 1u << 20;
-      const double mean = (double)nmax / (double)(nb * P);
-      if (cp >= 64 && (double)cp >= mean + 6.0 * sqrt(8.0 * mean + 1.0) + 16.0) cap = (uint32_t)cp;
-    }
+    // (a level that is counted already gains nothing from slots)
+    uint32_t cap = pl.may_slot && !b->slots_off && !counted[l] ? slot_capacity(c, nb * P, nmax) : 0;
     { ProfScope ps(c, b, KP_RP_PREP);
       hipLaunchKernelGGL(k_rp_tile_first, dim3(nwin / 256 + 1), dim3(256), 0, b->stream, b->d_base[l], (uint32_t)nb, n_p, b->d_tfb); }
     for (;;) {
@@ -628,9 +707,8 @@ static int partition_stage(const shk_ctx *c, ShkStageBufs *b, int src, uint64_t 
         lvl.slot_cap = cap;
         hipLaunchKernelGGL(k_rp_slot_cursors, dim3((uint32_t)((nb * P) / 256 + 1 < 4096 ? (nb * P) / 256 + 1 : 4096)), dim3(256), 0, b->stream, cursor, nb * P, cap);
       } else {
-        const bool ready = (l == 0 && hist0_ready) || (l == 1 && hist1_ready);
-        if (!ready && l == 0 && c->nlevels >= 2 && c->lv[0].bits + c->lv[1].bits <= 14 && c->lv[1].ng_log2 == 0 && !getenv("SHK_RP_HIST1")) {
-          // the first pass over unsorted words counts the second level's digits as well (k_rp_hist2)
+        // histogram, unless the producer or the level in front has counted this level
+        if (!counted[l] && pl.pair_hist) {
           HIPCHK(hipMemsetAsync(b->d_hist[0], 0, (P << c->lv[0].ng_log2) * 8, b->stream));
           HIPCHK(hipMemsetAsync(b->d_hist[1], 0, (P << c->lv[1].bits) * 8, b->stream));
           ProfScope ps(c, b, KP_RP_HIST);
@@ -638,8 +716,8 @@ static int partition_stage(const shk_ctx *c, ShkStageBufs *b, int src, uint64_t 
           for (int si = 0; si < nsrc; si++)
             hipLaunchKernelGGL((k_rp_hist2<14>), dim3(nwin / wt + 1), dim3(c->threads < 512 ? c->threads : 512), 0, b->stream, srcs[si].w, srcs[si].n_p,
                                c->lv[0], c->lv[1], b->d_hist[0], b->d_hist[1], wt);
-          hist1_ready = true;
-        } else if (!ready) {
+          counted[1] = true;
+        } else if (!counted[l]) {
           HIPCHK(hipMemsetAsync(b->d_hist[l], 0, ((nb * P) << c->lv[l].ng_log2) * 8, b->stream));
           ProfScope ps(c, b, KP_RP_HIST);
           const uint32_t wt = nwin / 4096 + 1;   // windows per workgroup
@@ -647,6 +725,7 @@ static int partition_stage(const shk_ctx *c, ShkStageBufs *b, int src, uint64_t 
             hipLaunchKernelGGL(k_rp_hist, dim3(nwin / wt + 1), dim3(c->threads), 0, b->stream, srcs[si].w, srcs[si].n_p, srcs[si].base, b->d_tfb, c->lv[l],
                                b->d_hist[l], wt);
         }
+        // bases
         if (c->lv[l].ng_log2) {
           // (first level only: nb = 1) sub-buckets in (digit, group) order; the next level's buckets are the digits
           const uint32_t ng = c->lv[l].ng_log2;
@@ -659,22 +738,23 @@ static int partition_stage(const shk_ctx *c, ShkStageBufs *b, int src, uint64_t 
           HIPCHK(hipMemcpyAsync(b->d_cursor, b->d_base[l + 1], nb * P * 8, hipMemcpyDeviceToDevice, b->stream));
         }
       }
+      // scatter
       { ProfScope ps(c, b, KP_RP_SCATTER);
         for (int si = 0; si < nsrc; si++) {
           const Src &S = srcs[si];
-          if (l == 0 && c->lv[0].ng_log2)      // (window groups are defined on the first level's 16384-key windows: SHK_RP_TILE0_LOG2)
-            hipLaunchKernelGGL((k_rp_scatter<SHK_RP_TILE0_LOG2, 1024>), dim3((uint32_t)(S.n >> SHK_RP_TILE0_LOG2) + 1), dim3(1024), 0, b->stream, S.w,
-                               b->d_words[cur ^ 1], S.n_p, S.base, b->d_tfb, lvl, cursor, b->d_err);
-          else if (c->threads >= 512 && l + 1 < c->nlevels && c->lv[l].bits <= 8 && !getenv("SHK_RP_NARROW"))
-            // a level in the middle: 16384-key windows as at the first level (digit runs of 1 KB instead of 256 bytes:
-            // 2.85 -> 2.25 ms per 832 M keys). Not the last level: its 4-byte records in slots gain nothing (3.4 ms either way)
-            hipLaunchKernelGGL((k_rp_scatter<SHK_RP_TILE0_LOG2, 1024, 256>), dim3((uint32_t)(S.n >> SHK_RP_TILE0_LOG2) + 1), dim3(1024), 0, b->stream, S.w,
-                               b->d_words[cur ^ 1], S.n_p, S.base, b->d_tfb, lvl, cursor, b->d_err);
+          const dim3 wide((uint32_t)(S.n >> SHK_RP_TILE0_LOG2) + 1);
+          if (pl.scatter == RP_SCATTER_GROUPED)      // (window groups are defined on the first level's 16384-key windows: SHK_RP_TILE0_LOG2)
+            hipLaunchKernelGGL((k_rp_scatter<SHK_RP_TILE0_LOG2, 1024>), wide, dim3(1024), 0, b->stream, S.w, b->d_words[cur ^ 1], S.n_p, S.base,
+                               b->d_tfb, lvl, cursor, b->d_err);
+          else if (pl.scatter == RP_SCATTER_WIDE)
+            hipLaunchKernelGGL((k_rp_scatter<SHK_RP_TILE0_LOG2, 1024, 256>), wide, dim3(1024), 0, b->stream, S.w, b->d_words[cur ^ 1], S.n_p, S.base,
+                               b->d_tfb, lvl, cursor, b->d_err);
           else
             hipLaunchKernelGGL((k_rp_scatter<12, SHK_RP_THREADS>), dim3((uint32_t)(S.n / SHK_RP_TILE + 1)), dim3(SHK_RP_THREADS), 0, b->stream, S.w,
                                b->d_words[cur ^ 1], S.n_p, S.base, b->d_tfb, lvl, cursor, b->d_err);
         } }
       if (!cap) break;
+      // slots: did every region fit?
       uint32_t bits = 0;
       if (fetch_err(b, &bits)) return SHK_ERR_HIP;
       if (bits & ~SHK_E_SLOT_FULL) return map_err_bits(bits & ~SHK_E_SLOT_FULL);
@@ -683,7 +763,6 @@ static int partition_stage(const shk_ctx *c, ShkStageBufs *b, int src, uint64_t 
       cap = 0;                               // a region overflowed its slot: the same level again with exact bases
     }
     cur ^= 1;
-    in = b->d_words[cur];
   }
   HIPCHK(hipGetLastError());
   *dst = cur;
@@ -704,11 +783,11 @@ static void launch_merge(shk_ctx *c, const ShkMergeArgs &A0, bool rec = false) {
     // (the write pass, MODE 1, has no record-sourced form: naming MODE 0 in its place keeps launch_merge<1> from
     // instantiating one that the test in front never lets run)
     if (MODE != 1 && rec)
-      hipLaunchKernelGGL((k_region_merge<MODE == 1 ? 0 : MODE, SHK_IMG_BLOCKS, false, true>), dim3(nblk), dim3(c->merge_group), 0, c->stream, A);
+      hipLaunchKernelGGL((k_region_merge<MODE == 1 ? 0 : MODE, SHK_IMG_BLOCKS, false, true>), dim3(nblk), dim3(SHK_MERGE_GROUP), 0, c->stream, A);
     else if (c->big_image)
-      hipLaunchKernelGGL((k_region_merge<MODE, SHK_IMG_BLOCKS_BIG>), dim3(nblk), dim3(c->merge_group), 0, c->stream, A);
+      hipLaunchKernelGGL((k_region_merge<MODE, SHK_IMG_BLOCKS_BIG>), dim3(nblk), dim3(SHK_MERGE_GROUP), 0, c->stream, A);
     else
-      hipLaunchKernelGGL((k_region_merge<MODE, SHK_IMG_BLOCKS>), dim3(nblk), dim3(c->merge_group), 0, c->stream, A);
+      hipLaunchKernelGGL((k_region_merge<MODE, SHK_IMG_BLOCKS>), dim3(nblk), dim3(SHK_MERGE_GROUP), 0, c->stream, A);
   }
 }
 
@@ -767,7 +846,7 @@ static void fill_args(shk_ctx *c, ShkMergeArgs *A, const uint64_t *words, uint32
   { const char *ab = getenv("SHK_ABLATE"); A->ablate = ab ? (uint32_t)atoi(ab) : 0; }
 #endif
   { const char *sp = getenv("SHK_STAMPS");    // diagnostics: "fused" = only the one-pass deNoise launches, "plain" = all the others, else all
-    A->dbg = (sp && strcmp(sp, "fused") != 0) ? (unsigned long long *)(c->d_scalars + 16) : nullptr; }
+    A->dbg = (sp && strcmp(sp, "fused") != 0) ? (unsigned long long *)(c->d_scalars + DS_STAMPS) : nullptr; }
   A->spill = spill_out(c); A->orec = c->spill[c->live]; A->over_list = c->d_over_list; A->n_over = c->d_counters + SHK_CNT_NOVER; A->list = nullptr;
   A->newchunks = nullptr; A->chist = nullptr;
   A->counted = c->counted;
@@ -819,17 +898,16 @@ static int merge_summary(shk_ctx *c, const uint64_t *words, uint32_t lo, uint32_
     HIPCHK(hipMemcpyAsync(c->h_chist, c->d_chist, ((uint64_t)hi + 1) * 8, hipMemcpyDeviceToHost, c->stream));
   }
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(c->h_pinned, c->d_counters, (SHK_CNT_NOVER + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipMemcpyAsync(c->h_pinned + 40, c->d_err, 4, hipMemcpyDeviceToHost, c->stream));
+  const uint64_t *cnt = c->h_pinned + HP_COUNTERS;
+  HIPCHK(hipMemcpyAsync(c->h_pinned + HP_COUNTERS, c->d_counters, (SHK_CNT_NOVER + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+  if (err_enqueue(c)) return SHK_ERR_HIP;
   HIPCHK(hipStreamSynchronize(c->stream));
-  o->newd = c->h_pinned[0]; o->added = c->h_pinned[1]; o->removed = c->h_pinned[2];
-  o->err = *(uint32_t *)(c->h_pinned + 40);
-  if (o->err) c->last_err_bits = o->err;
-  if (o->err) HIPCHK(hipMemsetAsync(c->d_err, 0, 16, c->stream));
+  o->newd = cnt[CNT_NEWD]; o->added = cnt[CNT_ADDED]; o->removed = cnt[CNT_REMOVED];
+  if (err_take(c, true, &o->err)) return SHK_ERR_HIP;
   c->chist_n = with_chist ? hi + 1 : 0;
   if (spill && !o->err) {
     c->spill_valid = 1; c->spill_words = words; c->spill_lo = lo; c->spill_hi = hi; c->spill_denoise = denoise;
-    c->spill_big = c->big_image; c->spill_nover = c->h_pinned[SHK_CNT_NOVER];
+    c->spill_big = c->big_image; c->spill_nover = cnt[SHK_CNT_NOVER];
   }
   return SHK_OK;
 }
@@ -883,7 +961,7 @@ static int denoise_round_once(shk_ctx *c, uint64_t *removed) {
   { int rc = table_sync(c); if (rc) return rc; }
   { ProfScope ps(c, KP_MARKS);
     hipLaunchKernelGGL(k_denoise_marks, dim3(1), dim3(64), 0, c->stream, c->tab[c->cur], c->nslots, c->xnslots, c->nblocks,
-                       ml, (unsigned long long *)(c->d_scalars + 3)); }
+                       ml, (unsigned long long *)(c->d_scalars + DS_MARKS)); }
   MergeOut o;
   int rc = merge_summary(c, nullptr, 0, 0, 1, &o, false, true);
   if (rc) return rc;
@@ -905,7 +983,7 @@ static int denoise_with_rest(shk_ctx *c, const uint64_t *words, uint32_t lo, uin
   { int rc = table_sync(c); if (rc) return rc; }
   { ProfScope ps(c, KP_MARKS);
     hipLaunchKernelGGL(k_denoise_marks, dim3(1), dim3(64), 0, c->stream, c->tab[c->cur], c->nslots, c->xnslots, c->nblocks,
-                       ml, (unsigned long long *)(c->d_scalars + 3)); }
+                       ml, (unsigned long long *)(c->d_scalars + DS_MARKS)); }
   MergeOut o;
   int rc = merge_summary(c, words, lo, hi, 1, &o, false, true);
   if (rc) return rc;
@@ -970,13 +1048,12 @@ static void point_scans(shk_ctx *c, bool final_table, bool inter_table, long lon
 
 static int point_read(shk_ctx *c, PointOut *po) {
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(c->h_pinned, c->d_counters, SHK_NCOUNTERS * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipMemcpyAsync(c->h_pinned + 40, c->d_err, 4, hipMemcpyDeviceToHost, c->stream));
+  const uint64_t *cnt = c->h_pinned + HP_COUNTERS;
+  HIPCHK(hipMemcpyAsync(c->h_pinned + HP_COUNTERS, c->d_counters, SHK_NCOUNTERS * 8, hipMemcpyDeviceToHost, c->stream));
+  if (err_enqueue(c)) return SHK_ERR_HIP;
   HIPCHK(hipStreamSynchronize(c->stream));
-  po->newd_after = c->h_pinned[0]; po->added_after = c->h_pinned[1]; po->removed = c->h_pinned[2]; po->added_before = c->h_pinned[3];
-  po->err = *(uint32_t *)(c->h_pinned + 40);
-  if (po->err) HIPCHK(hipMemsetAsync(c->d_err, 0, 16, c->stream));
-  return SHK_OK;
+  po->newd_after = cnt[CNT_NEWD]; po->added_after = cnt[CNT_ADDED]; po->removed = cnt[CNT_REMOVED]; po->added_before = cnt[CNT_ADDED_BEFORE];
+  return err_take(c, false, &po->err);
 }
 
 // with_chist: the pass also records the first chunk of every key the table has not seen; c->h_chist[lo..hi] afterwards
@@ -992,14 +1069,14 @@ static int point_try(shk_ctx *c, const uint64_t *words, uint32_t lo, uint32_t sp
     HIPCHK(hipMemsetAsync(c->d_chist, 0, SHK_MAX_CHUNKS * 8, c->stream));
   }
   { const char *sp = getenv("SHK_STAMPS");
-    A.dbg = (sp && strcmp(sp, "plain") != 0) ? (unsigned long long *)(c->d_scalars + 16) : nullptr; }
+    A.dbg = (sp && strcmp(sp, "plain") != 0) ? (unsigned long long *)(c->d_scalars + DS_STAMPS) : nullptr; }
   c->spill_valid = 0;
   c->chist_n = 0;
   HIPCHK(hipMemsetAsync(c->d_counters, 0, SHK_NCOUNTERS * 8, c->stream));
   { ProfScope ps(c, KP_MERGE_FUSED);
     SHK_FOR_REGION_SLICES(c, A, nblk) {
-      if (c->rec_live) hipLaunchKernelGGL((k_region_merge<3, SHK_IMG_BLOCKS, true, true>), dim3(nblk), dim3(c->merge_group), 0, c->stream, A);
-      else hipLaunchKernelGGL((k_region_merge<3, SHK_IMG_BLOCKS, true>), dim3(nblk), dim3(c->merge_group), 0, c->stream, A);
+      if (c->rec_live) hipLaunchKernelGGL((k_region_merge<3, SHK_IMG_BLOCKS, true, true>), dim3(nblk), dim3(SHK_MERGE_GROUP), 0, c->stream, A);
+      else hipLaunchKernelGGL((k_region_merge<3, SHK_IMG_BLOCKS, true>), dim3(nblk), dim3(SHK_MERGE_GROUP), 0, c->stream, A);
     } }
   point_scans(c, true, true, 0);
   if (with_chist) {
@@ -1008,13 +1085,13 @@ static int point_try(shk_ctx *c, const uint64_t *words, uint32_t lo, uint32_t sp
                        c->d_newchunks, c->d_summary, c->nregions, c->d_chist, 1u);
     HIPCHK(hipMemcpyAsync(c->h_chist, c->d_chist, ((uint64_t)hi + 1) * 8, hipMemcpyDeviceToHost, c->stream));
   }
-  HIPCHK(hipMemcpyAsync(c->h_pinned + 48, c->d_fin_i + c->nregions, 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipMemcpyAsync(c->h_pinned + 49, c->d_ilens, 1, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(c->h_pinned + HP_IFIN, c->d_fin_i + c->nregions, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(c->h_pinned + HP_IFIRST, c->d_ilens, 1, hipMemcpyDeviceToHost, c->stream));
   rc = point_read(c, po);
   if (rc) return rc;
-  po->islots = c->h_pinned[SHK_CNT_ISLOTS];
-  po->ifin = c->h_pinned[48];
-  po->first_used = (c->h_pinned[49] & 0xff) != 0;
+  po->islots = c->h_pinned[HP_COUNTERS + SHK_CNT_ISLOTS];
+  po->ifin = c->h_pinned[HP_IFIN];
+  po->first_used = (c->h_pinned[HP_IFIRST] & 0xff) != 0;
   if (with_chist && !po->err) c->chist_n = hi + 1;
   return SHK_OK;
 }
@@ -1025,22 +1102,20 @@ static int point_walk(shk_ctx *c, long long carry, const ShkWalkShard &W, const 
                       uint64_t *nprot, uint32_t *err) {
   const uint64_t ml = c->cfg.min_denoise_len ? c->cfg.min_denoise_len : (1ULL << 20);
   if (carry > 0) point_scans(c, false, true, carry);      // the layout as it is in the single table
-  c->h_pinned[50] = state_in[0]; c->h_pinned[51] = state_in[1];
-  HIPCHK(hipMemcpyAsync(c->d_scalars + 8, c->h_pinned + 50, 16, hipMemcpyHostToDevice, c->stream));
+  c->h_pinned[HP_WALK_IN] = state_in[0]; c->h_pinned[HP_WALK_IN + 1] = state_in[1];
+  HIPCHK(hipMemcpyAsync(c->d_scalars + DS_WALK_IN, c->h_pinned + HP_WALK_IN, 16, hipMemcpyHostToDevice, c->stream));
   { ProfScope ps(c, KP_MARKS);
     hipLaunchKernelGGL(k_denoise_marks_virtual, dim3(1), dim3(64), 0, c->stream, (const uint64_t *)c->d_fin_i, (const uint8_t *)c->d_ilens,
-                       (const uint32_t *)c->d_isum, c->nslots, c->xnslots, ml, c->d_prot, SHK_PROT_CAP, (unsigned long long *)(c->d_scalars + 3),
-                       W, (const uint64_t *)(c->d_scalars + 8), c->d_scalars + 10); }
+                       (const uint32_t *)c->d_isum, c->nslots, c->xnslots, ml, c->d_prot, SHK_PROT_CAP, (unsigned long long *)(c->d_scalars + DS_MARKS),
+                       W, (const uint64_t *)(c->d_scalars + DS_WALK_IN), c->d_scalars + DS_WALK_OUT); }
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(c->h_pinned + 47, c->d_scalars + 3, 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipMemcpyAsync(c->h_pinned + 52, c->d_scalars + 10, 16, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipMemcpyAsync(c->h_pinned + 40, c->d_err, 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(c->h_pinned + HP_MARKS, c->d_scalars + DS_MARKS, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(c->h_pinned + HP_WALK_OUT, c->d_scalars + DS_WALK_OUT, 16, hipMemcpyDeviceToHost, c->stream));
+  if (err_enqueue(c)) return SHK_ERR_HIP;
   HIPCHK(hipStreamSynchronize(c->stream));
-  *nprot = c->h_pinned[47];
-  state_out[0] = c->h_pinned[52]; state_out[1] = c->h_pinned[53];
-  *err = *(uint32_t *)(c->h_pinned + 40);
-  if (*err) HIPCHK(hipMemsetAsync(c->d_err, 0, 16, c->stream));
-  return SHK_OK;
+  *nprot = c->h_pinned[HP_MARKS];
+  state_out[0] = c->h_pinned[HP_WALK_OUT]; state_out[1] = c->h_pinned[HP_WALK_OUT + 1];
+  return err_take(c, false, err);
 }
 
 // the regions that hold a protected singleton, once more with the list; statistics of the whole pass again
@@ -1059,8 +1134,8 @@ static int point_finish(shk_ctx *c, const uint64_t *words, uint32_t lo, uint32_t
     HIPCHK(hipMemcpyAsync(c->d_over_list, regs.data(), regs.size() * 4, hipMemcpyHostToDevice, c->stream));
     A.list = c->d_over_list; A.prot_list = c->d_prot; A.nprot = (uint32_t)nprot;
     { ProfScope ps(c, KP_MISC);   // (the same old side as the first go: its records are untouched)
-      if (c->rec_live) hipLaunchKernelGGL((k_region_merge<3, SHK_IMG_BLOCKS, true, true>), dim3((uint32_t)regs.size()), dim3(c->merge_group), 0, c->stream, A);
-      else hipLaunchKernelGGL((k_region_merge<3, SHK_IMG_BLOCKS, true>), dim3((uint32_t)regs.size()), dim3(c->merge_group), 0, c->stream, A); }
+      if (c->rec_live) hipLaunchKernelGGL((k_region_merge<3, SHK_IMG_BLOCKS, true, true>), dim3((uint32_t)regs.size()), dim3(SHK_MERGE_GROUP), 0, c->stream, A);
+      else hipLaunchKernelGGL((k_region_merge<3, SHK_IMG_BLOCKS, true>), dim3((uint32_t)regs.size()), dim3(SHK_MERGE_GROUP), 0, c->stream, A); }
     HIPCHK(hipStreamSynchronize(c->stream));   // (regs lives on this stack frame)
     point_scans(c, true, false, 0);
     int rc = point_read(c, po);
@@ -1165,19 +1240,17 @@ static int sample_pass(shk_ctx *c, const uint64_t *words, uint32_t lo, uint32_t 
     for (uint32_t r0 = 0; r0 < ns; r0 += SHK_REGION_SLICE) {
       A.r0 = r0;
       const uint32_t nblk = ns - r0 < SHK_REGION_SLICE ? ns - r0 : SHK_REGION_SLICE;
-      if (c->rec_live) hipLaunchKernelGGL((k_region_merge<0, SHK_IMG_BLOCKS, false, true>), dim3(nblk), dim3(c->merge_group), 0, c->stream, A);
-      else hipLaunchKernelGGL((k_region_merge<0, SHK_IMG_BLOCKS>), dim3(nblk), dim3(c->merge_group), 0, c->stream, A);
+      if (c->rec_live) hipLaunchKernelGGL((k_region_merge<0, SHK_IMG_BLOCKS, false, true>), dim3(nblk), dim3(SHK_MERGE_GROUP), 0, c->stream, A);
+      else hipLaunchKernelGGL((k_region_merge<0, SHK_IMG_BLOCKS>), dim3(nblk), dim3(SHK_MERGE_GROUP), 0, c->stream, A);
     }
     hipLaunchKernelGGL(k_chunk_hist, dim3((ns + SHK_CHIST_REGIONS - 1) / SHK_CHIST_REGIONS), dim3(256), 0, c->stream,
                        c->d_newchunks, c->d_summary, c->nregions, c->d_chist, stride); }
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(c->h_chist, c->d_chist, ((uint64_t)hi + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipMemcpyAsync(c->h_pinned + 40, c->d_err, 4, hipMemcpyDeviceToHost, c->stream));
+  if (err_enqueue(c)) return SHK_ERR_HIP;
   HIPCHK(hipStreamSynchronize(c->stream));
-  *err_out = *(uint32_t *)(c->h_pinned + 40);
-  if (*err_out) HIPCHK(hipMemsetAsync(c->d_err, 0, 16, c->stream));   // whatever it is, the full pass will meet it again and deal with it
   *ns_out = ns;
-  return SHK_OK;
+  return err_take(c, false, err_out);   // (cleared: whatever it is, the full pass will meet it again and deal with it)
 }
 
 // verdict 0: no point expected in [lo, hi]; 1: expected at chunk *guess; 2: cannot tell
@@ -1353,18 +1426,17 @@ static int finish(shk_ctx *c, int rc) {
 static int front_end(const shk_ctx *c, ShkStageBufs *b, const void *text, int on_device, uint64_t text_bytes, const uint64_t *chunk_off,
                      const uint64_t *chunk_len, uint32_t nchunks, uint64_t *nwords, int *dst, uint32_t *region_cap) {
   const bool roll = roll_path(c);
-  bool h1 = false;
-  int rc = roll ? roll_stage(c, b, text, on_device, text_bytes, chunk_off, chunk_len, nchunks, 0, 1, &h1)
+  // (one-level contexts: the hash kernel, which counts the level's digits as it goes)
+  int rc = roll ? roll_stage(c, b, text, on_device, text_bytes, chunk_off, chunk_len, nchunks, 0, 1)
                 : hash_stage(c, b, text, on_device, text_bytes, chunk_off, chunk_len, nchunks, 0, 1, true);
   if (rc) return rc;
   uint32_t bits = 0;
-  HIPCHK(hipMemcpyAsync(b->h_pinned + 42, b->d_scalars + 1, 8, hipMemcpyDeviceToHost, b->stream));
+  HIPCHK(hipMemcpyAsync(b->h_pinned + HP_NWORDS, b->d_scalars + DS_NWORDS, 8, hipMemcpyDeviceToHost, b->stream));
   if (fetch_err(b, &bits)) return SHK_ERR_HIP;
   if (bits) return map_err_bits(bits);
-  *nwords = b->h_pinned[42];
+  *nwords = b->h_pinned[HP_NWORDS];
   if (*nwords > c->cfg.max_batch_keys) return SHK_ERR_BATCH;
-  // (the roll kernels leave the words partitioned by the first digit; the hash kernel has counted the first level's digits)
-  rc = roll ? partition_stage(c, b, 0, *nwords, dst, nullptr, false, 1, h1) : partition_stage(c, b, 0, *nwords, dst, nullptr, true);
+  rc = partition_stage(c, b, roll ? part_from_roll(c, b, *nwords) : part_from_hash(b, *nwords), dst);
   *region_cap = b->region_cap;
   return rc;
 }
@@ -1564,21 +1636,17 @@ extern "C" int shk_hash_chunks(shk_ctx *c, const void *text, int text_on_device,
   if (upload_wait(c, text, text_on_device, c->stream)) return SHK_ERR_HIP;
   int rc = hash_stage(c, c, text, text_on_device, text_bytes, chunk_off, chunk_len, nchunks, c->cfg.shard_index, c->cfg.num_shards ? c->cfg.num_shards : 1);
   if (rc) return finish(c, rc);
-  HIPCHK(hipMemcpyAsync(c->h_pinned + 42, c->d_scalars + 1, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(c->h_pinned + HP_NWORDS, c->d_scalars + DS_NWORDS, 8, hipMemcpyDeviceToHost, c->stream));
   rc = finish(c, 0);
   *d_words = c->d_words[0];
-  *nwords = c->h_pinned[42];
+  *nwords = c->h_pinned[HP_NWORDS];
   return rc;
 }
 
-// External words -> partitioned by region in d_words[*dst]: their number goes to d_scalars[1], and the first partition
-// level reads the caller's buffer in place (no staging copy), be it one of the context's own or not.
+// external words -> partitioned by region in d_words[*dst]
 static int partition_words(shk_ctx *c, const uint64_t *d_words, uint64_t nwords, int *dst) {
-  c->h_pinned[43] = nwords;
-  HIPCHK(hipMemcpyAsync(c->d_scalars + 1, c->h_pinned + 43, 8, hipMemcpyHostToDevice, c->stream));
-  return d_words == c->d_words[0] ? partition_stage(c, c, 0, nwords, dst)
-       : d_words == c->d_words[1] ? partition_stage(c, c, 1, nwords, dst)
-                                  : partition_stage(c, c, 0, nwords, dst, d_words);
+  if (set_nwords(c, nwords)) return SHK_ERR_HIP;
+  return partition_stage(c, c, part_from_words(c, d_words, nwords), dst);
 }
 
 extern "C" int shk_count_words(shk_ctx *c, const uint64_t *d_words, uint64_t nwords, uint32_t nchunks,
@@ -1596,15 +1664,34 @@ extern "C" int shk_count_words(shk_ctx *c, const uint64_t *d_words, uint64_t nwo
   return finish(c, rc);
 }
 
-// where routed words go: one of two alternating send buffers (allocated on first use), or d_words[1] when
-// SHK_ROUTE_SINGLE_BUFFER is set
+// where routed words go: one of two alternating send buffers (allocated on first use)
 static int send_buffer(shk_ctx *c, uint64_t **send) {
-  *send = c->d_words[1];
-  if (getenv("SHK_ROUTE_SINGLE_BUFFER")) return SHK_OK;
   const int b = c->send_next;
   if (!c->d_send[b] && dmalloc(&c->d_send[b], c->cfg.max_batch_keys + 1)) return SHK_ERR_HIP;
   *send = c->d_send[b];
   c->send_next ^= 1;
+  return SHK_OK;
+}
+
+// Owner bins of the two routing calls, in d_block_sums (nbins <= 1024): the counters a histogram pass fills at ROUTE_HIST,
+// the cursors its scatter pass takes at ROUTE_CURSOR. Zeroes the counters, has `count` launch the histogram pass, and
+// turns the counts into the words per owner (per_owner consecutive bins each), the bins' bases (base[nbins] = all words;
+// the caller's, so that it outlives the copy) and the cursors. Kernel errors so far are the return code.
+enum { ROUTE_HIST = 0, ROUTE_CURSOR = 4096 };
+template <typename F>
+static int owner_bins(shk_ctx *c, uint32_t nbins, uint32_t per_owner, F count, uint64_t *counts, std::vector<uint64_t> &base) {
+  uint64_t *hist = c->d_block_sums + ROUTE_HIST;
+  HIPCHK(hipMemsetAsync(hist, 0, nbins * 8, c->stream));
+  count();
+  std::vector<uint64_t> hh(nbins);
+  HIPCHK(hipMemcpyAsync(hh.data(), hist, nbins * 8, hipMemcpyDeviceToHost, c->stream));
+  uint32_t bits = 0;
+  if (fetch_err(c, &bits)) return SHK_ERR_HIP;
+  if (bits) return map_err_bits(bits);
+  base.assign(nbins + 1, 0);
+  std::fill(counts, counts + nbins / per_owner, 0);
+  for (uint32_t i = 0; i < nbins; i++) { counts[i / per_owner] += hh[i]; base[i + 1] = base[i] + hh[i]; }
+  HIPCHK(hipMemcpyAsync(c->d_block_sums + ROUTE_CURSOR, base.data(), nbins * 8, hipMemcpyHostToDevice, c->stream));
   return SHK_OK;
 }
 
@@ -1626,28 +1713,22 @@ extern "C" int shk_route_words(shk_ctx *c, uint64_t nwords, uint32_t nshards, ui
   ShkRpLevel lv;
   lv.shift = (c->cfg.qb - SHK_REGION_LOG2) - lg; lv.bits = lg; lv.nbuckets = 1; lv.hb = c->cfg.hb; lv.q_lo = 0;
   lv.nslots = ~0ULL; lv.out32 = 0; lv.ablate = 0; lv.ng_log2 = 0; lv.slot_cap = 0;
-  c->h_pinned[43] = nwords;
-  HIPCHK(hipMemcpyAsync(c->d_scalars + 1, c->h_pinned + 43, 8, hipMemcpyHostToDevice, c->stream));
-  const uint64_t *n_p = c->d_scalars + 1;
+  if (set_nwords(c, nwords)) return SHK_ERR_HIP;
+  const uint64_t *n_p = c->d_scalars + DS_NWORDS;
   const uint32_t nwin = (uint32_t)(nwords / SHK_RP_TILE + 1);
-  uint64_t *hist = c->d_block_sums;            // scratch: nshards <= 1024 words each
-  uint64_t *cursor = c->d_block_sums + 4096;
   { ProfScope ps(c, KP_RP_PREP);
     hipLaunchKernelGGL(k_rp_base1, dim3(1), dim3(64), 0, c->stream, n_p, c->d_base[0]);
-    hipLaunchKernelGGL(k_rp_tile_first, dim3(nwin / 256 + 1), dim3(256), 0, c->stream, c->d_base[0], 1u, n_p, c->d_tfb);
-    HIPCHK(hipMemsetAsync(hist, 0, nshards * 8, c->stream)); }
-  { ProfScope ps(c, KP_RP_HIST);
+    hipLaunchKernelGGL(k_rp_tile_first, dim3(nwin / 256 + 1), dim3(256), 0, c->stream, c->d_base[0], 1u, n_p, c->d_tfb); }
+  std::vector<uint64_t> base;
+  int rc = owner_bins(c, nshards, 1, [&] {
+    ProfScope ps(c, KP_RP_HIST);
     const uint32_t wt = nwin / 4096 + 1;
-    hipLaunchKernelGGL(k_rp_hist, dim3(nwin / wt + 1), dim3(c->threads), 0, c->stream, c->d_words[0], n_p, c->d_base[0], c->d_tfb, lv, hist, wt); }
-  std::vector<uint64_t> hh(nshards);
-  HIPCHK(hipMemcpyAsync(hh.data(), hist, nshards * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  std::vector<uint64_t> bb(nshards + 1, 0);
-  for (uint32_t i = 0; i < nshards; i++) { counts[i] = hh[i]; bb[i + 1] = bb[i] + hh[i]; }
-  HIPCHK(hipMemcpyAsync(cursor, bb.data(), nshards * 8, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_rp_hist, dim3(nwin / wt + 1), dim3(c->threads), 0, c->stream, c->d_words[0], n_p, c->d_base[0], c->d_tfb, lv, c->d_block_sums + ROUTE_HIST, wt);
+  }, counts, base);
+  if (rc) return finish(c, rc);
   { ProfScope ps(c, KP_RP_SCATTER);
     hipLaunchKernelGGL((k_rp_scatter<12, SHK_RP_THREADS>), dim3(nwin), dim3(SHK_RP_THREADS), 0, c->stream, c->d_words[0], send, n_p,
-                       c->d_base[0], c->d_tfb, lv, cursor, c->d_err); }
+                       c->d_base[0], c->d_tfb, lv, c->d_block_sums + ROUTE_CURSOR, c->d_err); }
   HIPCHK(hipGetLastError());
   *d_out = send;
   return finish(c, 0);
@@ -1681,30 +1762,23 @@ extern "C" int shk_hash_route_chunks(shk_ctx *c, const void *text, int text_on_d
   const uint32_t rb = c->cfg.qb - SHK_REGION_LOG2;
   const uint32_t db = lg > 7 ? lg : (rb < 7 ? (rb > lg ? rb : lg) : 7);
   const uint32_t nbins = 1u << db, per_owner = nbins / nshards;
-  uint64_t *hist = c->d_block_sums;            // scratch: nbins <= 1024 words each
-  uint64_t *cursor = c->d_block_sums + 4096;
   ShkRollArgs A;
   roll_args(c, c, A, dtext, text_bytes, chunk_first, chunk_mul);
   A.q_lo = 0;                                   // (owners are ranges of the WHOLE filter's quotients)
   A.dig_shift = rb - db; A.dig_bits = db;
   A.hist_shift = A.dig_shift; A.hist_bits = db;
-  A.hist = hist; A.cursor = cursor; A.out = send;
+  A.hist = c->d_block_sums + ROUTE_HIST; A.cursor = c->d_block_sums + ROUTE_CURSOR; A.out = send;
   rc = pack_stage(c, c, A, nreads, text_bytes, c->d_words[0]);      // (d_words[0]: filled by shk_stage_words, after this call)
   if (rc) return finish(c, rc);
-  HIPCHK(hipMemsetAsync(hist, 0, nbins * 8, c->stream));     // (behind pack_stage, whose scan uses the head of d_block_sums too)
-  { ProfScope ps(c, KP_ROLL_HIST);
-    launch_roll_hist(c, c, A, nreads, false); }
-  std::vector<uint64_t> hh(nbins);
-  HIPCHK(hipMemcpyAsync(hh.data(), hist, nbins * 8, hipMemcpyDeviceToHost, c->stream));
-  uint32_t bits = 0;
-  if (fetch_err(c, &bits)) return SHK_ERR_HIP;
-  if (bits) { prof_collect(c); return map_err_bits(bits); }
-  std::vector<uint64_t> bb(nbins + 1, 0);
-  for (uint32_t i = 0; i < nshards; i++) counts[i] = 0;
-  for (uint32_t i = 0; i < nbins; i++) { counts[i / per_owner] += hh[i]; bb[i + 1] = bb[i] + hh[i]; }
-  *nwords = bb[nbins];
-  if (bb[nbins] > c->cfg.max_batch_keys) { prof_collect(c); return SHK_ERR_BATCH; }
-  HIPCHK(hipMemcpyAsync(cursor, bb.data(), nbins * 8, hipMemcpyHostToDevice, c->stream));
+  // (the bins are zeroed behind pack_stage, whose scan uses the head of d_block_sums too)
+  std::vector<uint64_t> base;
+  rc = owner_bins(c, nbins, per_owner, [&] {
+    ProfScope ps(c, KP_ROLL_HIST);
+    launch_roll_hist(c, c, A, nreads, false);
+  }, counts, base);
+  if (rc) return finish(c, rc);
+  *nwords = base[nbins];
+  if (base[nbins] > c->cfg.max_batch_keys) return finish(c, SHK_ERR_BATCH);
   launch_roll_scatter(c, c, A, nreads);
   HIPCHK(hipGetLastError());
   *d_out = send;
@@ -1732,14 +1806,13 @@ extern "C" int shk_stage_words_pair(shk_ctx *c, const uint64_t *d_a, uint64_t na
     if ((d_a + na > o0 && d_a < o1) || (d_b + nb > o0 && d_b < o1)) return SHK_ERR_ARG; }
   if (c->nlevels == 0) return SHK_ERR_ARG;       // (a single region has no partition to read two sources: concatenate)
   HIPCHK(hipSetDevice(c->dev));
-  c->h_pinned[43] = na + nb;
-  c->h_pinned[56] = na; c->h_pinned[57] = nb; c->h_pinned[58] = 0; c->h_pinned[59] = na; c->h_pinned[60] = 0; c->h_pinned[61] = nb;
-  HIPCHK(hipMemcpyAsync(c->d_scalars + 1, c->h_pinned + 43, 8, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(c->d_scalars + 40, c->h_pinned + 56, 48, hipMemcpyHostToDevice, c->stream));
-  c->stage2_b = d_b; c->stage2_na = na; c->stage2_nb = nb;
+  if (set_nwords(c, na + nb)) return SHK_ERR_HIP;
+  // the sources' lengths (DS_PAIR_LEN) and their one-bucket base arrays (DS_PAIR_BASE)
+  const uint64_t pair[DS_END - DS_PAIR_LEN] = {na, nb, 0, na, 0, nb};
+  memcpy(c->h_pinned + HP_PAIR, pair, sizeof(pair));
+  HIPCHK(hipMemcpyAsync(c->d_scalars + DS_PAIR_LEN, c->h_pinned + HP_PAIR, sizeof(pair), hipMemcpyHostToDevice, c->stream));
   int dst = 0;
-  int rc = partition_stage(c, c, 0, na + nb, &dst, d_a);
-  c->stage2_b = nullptr;
+  int rc = partition_stage(c, c, part_from_words(c, d_a, na, d_b, nb), &dst);
   c->staged = dst;
   return finish(c, rc);
 }
@@ -1823,7 +1896,7 @@ extern "C" int shk_stage_try_denoise(shk_ctx *c, uint32_t lo, uint32_t hi, shk_s
   { int rc = table_sync(c); if (rc) return rc; }
   { ProfScope ps(c, KP_MARKS);
     hipLaunchKernelGGL(k_denoise_marks, dim3(1), dim3(64), 0, c->stream, c->tab[c->cur], c->nslots, c->xnslots, c->nblocks,
-                       ml, (unsigned long long *)(c->d_scalars + 3)); }
+                       ml, (unsigned long long *)(c->d_scalars + DS_MARKS)); }
   MergeOut o;
   int rc = merge_summary(c, c->d_words[c->staged], lo, hi, 1, &o, false, true);
   prof_collect(c);
@@ -1937,9 +2010,9 @@ extern "C" int shk_stats(shk_ctx *c, shk_totals *o) {
   HIPCHK(hipSetDevice(c->dev));
   o->nelts = c->nelts; o->ndistinct = c->ndistinct; o->rounds_left = c->rounds_left; o->rounds_done = c->rounds_done;
   o->nslots = c->nslots; o->xnslots = c->xnslots; o->nblocks = c->nblocks; o->table_bytes = c->table_bytes;
-  HIPCHK(hipMemcpyAsync(c->h_pinned + 44, c->fin[c->cur] + c->nregions, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(c->h_pinned + HP_FREE_PTR, c->fin[c->cur] + c->nregions, 8, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
-  o->free_pointer = c->h_pinned[44];
+  o->free_pointer = c->h_pinned[HP_FREE_PTR];
   return SHK_OK;
 }
 
@@ -2100,28 +2173,27 @@ extern "C" int shk_insert_counted(shk_ctx *c, const uint64_t *keys, const uint64
     uint64_t skip = 0, maxc = 0;
     bool halve = false;
     do {
-      HIPCHK(hipMemsetAsync(c->d_scalars + 4, 0, 8, c->stream));
+      HIPCHK(hipMemsetAsync(c->d_scalars + DS_MAX_COUNT, 0, 8, c->stream));
       const uint32_t nb = (uint32_t)((m + 255) / 256);
       { ProfScope ps(c, KP_MISC);
         hipLaunchKernelGGL(k_expand_counted<0>, dim3(nb), dim3(256), 0, c->stream, dk + done, dc + done, m, skip, take, c->cfg.hb, dnw,
-                           (const uint64_t *)nullptr, (uint64_t *)nullptr, c->d_err, key_lo, key_hi, (unsigned long long *)(c->d_scalars + 4)); }
+                           (const uint64_t *)nullptr, (uint64_t *)nullptr, c->d_err, key_lo, key_hi, (unsigned long long *)(c->d_scalars + DS_MAX_COUNT)); }
       if (run_scan<uint32_t>(c, c, dnw, m, nullptr, doff)) { rc = SHK_ERR_HIP; break; }
-      HIPCHK(hipMemcpyAsync(c->h_pinned + 45, doff + m, 8, hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(hipMemcpyAsync(c->h_pinned + 46, c->d_scalars + 4, 8, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(hipMemcpyAsync(c->h_pinned + HP_TOTAL, doff + m, 8, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(hipMemcpyAsync(c->h_pinned + HP_AUX, c->d_scalars + DS_MAX_COUNT, 8, hipMemcpyDeviceToHost, c->stream));
       uint32_t bits = 0;
       if (fetch_err(c, &bits)) { rc = SHK_ERR_HIP; break; }
       if (bits) { rc = map_err_bits(bits); break; }
-      const uint64_t nwords = c->h_pinned[45];
-      maxc = c->h_pinned[46];
+      const uint64_t nwords = c->h_pinned[HP_TOTAL];
+      maxc = c->h_pinned[HP_AUX];
       if (nwords > c->cfg.max_batch_keys) { halve = true; break; }
       if (nwords) {
         { ProfScope ps(c, KP_MISC);
           hipLaunchKernelGGL(k_expand_counted<1>, dim3(nb), dim3(256), 0, c->stream, dk + done, dc + done, m, skip, take, c->cfg.hb, dnw,
                              doff, c->d_words[0], c->d_err, key_lo, key_hi, (unsigned long long *)nullptr); }
-        c->h_pinned[43] = nwords;
-        HIPCHK(hipMemcpyAsync(c->d_scalars + 1, c->h_pinned + 43, 8, hipMemcpyHostToDevice, c->stream));
+        if (set_nwords(c, nwords)) return SHK_ERR_HIP;
         int dst = 0;
-        rc = partition_stage(c, c, 0, nwords, &dst);
+        rc = partition_stage(c, c, part_from_words(c, c->d_words[0], nwords), &dst);
         if (rc) break;
         MergeOut o;
         rc = merge_plain(c, c->d_words[dst], &o);
@@ -2157,7 +2229,7 @@ extern "C" int shk_dump(shk_ctx *c, uint64_t *keys, uint64_t *counts, uint64_t c
   fill_args(c, &A, nullptr, 0, 0, 0);
   uint32_t *nper = c->d_over_list;                       // scratch of the spill scheme: [nregions + 1]
   uint64_t *offs = c->d_dump_offs;                       // [nregions + 2]
-  unsigned long long *stop = (unsigned long long *)(c->d_scalars + 5);
+  unsigned long long *stop = (unsigned long long *)(c->d_scalars + DS_DUMP_STOP);
   const uint64_t *no_offs = nullptr;
   uint64_t *no_out = nullptr;
   c->spill_valid = 0;
@@ -2174,16 +2246,16 @@ extern "C" int shk_dump(shk_ctx *c, uint64_t *keys, uint64_t *counts, uint64_t c
     break;
   }
   if (run_scan<uint32_t>(c, c, nper, c->nregions, nullptr, offs)) return SHK_ERR_HIP;
-  HIPCHK(hipMemcpyAsync(c->h_pinned + 45, offs + c->nregions, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(c->h_pinned + HP_TOTAL, offs + c->nregions, 8, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
-  const uint64_t total = c->h_pinned[45];
+  const uint64_t total = c->h_pinned[HP_TOTAL];
   *n_out = total;
   if (!keys && !ref_iterator_end) return finish(c, 0);
   const uint64_t m = keys ? (total < cap ? total : cap) : 0;
   uint64_t *dk = keys, *dc = counts;
   if (!on_device && m) { if (dmalloc(&dk, m) || dmalloc(&dc, m)) return SHK_ERR_HIP; }
-  c->h_pinned[46] = ~0ULL;
-  HIPCHK(hipMemcpyAsync(stop, c->h_pinned + 46, 8, hipMemcpyHostToDevice, c->stream));
+  c->h_pinned[HP_AUX] = ~0ULL;
+  HIPCHK(hipMemcpyAsync(stop, c->h_pinned + HP_AUX, 8, hipMemcpyHostToDevice, c->stream));
   if (total) {
     ProfScope ps(c, KP_MISC);
     unsigned long long *sp = ref_iterator_end ? stop : nullptr;
@@ -2193,14 +2265,14 @@ extern "C" int shk_dump(shk_ctx *c, uint64_t *keys, uint64_t *counts, uint64_t c
     }
   }
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(c->h_pinned + 46, stop, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(c->h_pinned + HP_AUX, stop, 8, hipMemcpyDeviceToHost, c->stream));
   if (!on_device && m) {
     HIPCHK(hipMemcpyAsync(keys, dk, m * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(counts, dc, m * 8, hipMemcpyDeviceToHost, c->stream));
   }
   HIPCHK(hipStreamSynchronize(c->stream));
   if (!on_device && m) { hipFree(dk); hipFree(dc); }
-  if (ref_iterator_end && c->h_pinned[46] < total) *n_out = c->h_pinned[46];
+  if (ref_iterator_end && c->h_pinned[HP_AUX] < total) *n_out = c->h_pinned[HP_AUX];
   return finish(c, 0);
 }
 
@@ -2225,12 +2297,12 @@ static int merge2_run(shk_ctx *c, const ShkSrc2 &S, uint64_t *newd_out, uint64_t
       hipLaunchKernelGGL(k_region_scan_c, dim3(ntiles), dim3(c->threads), 0, c->stream, c->d_summary, c->nregions, c->d_tile_f,
                          c->xnslots, (uint32_t)(c->big_image ? SHK_IMG_BLOCKS_BIG * 64 : SHK_IMG_SLOTS), c->fin[c->cur ^ 1], c->d_counters, c->d_err); }
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(c->h_pinned, c->d_counters, 4 * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(c->h_pinned + HP_COUNTERS, c->d_counters, 4 * 8, hipMemcpyDeviceToHost, c->stream));
     uint32_t bits = 0;
     if (fetch_err(c, &bits)) return SHK_ERR_HIP;
     if (!c->big_image && (bits & (SHK_E_OLD_EXTENT | SHK_E_NEW_EXTENT)) && !(bits & SHK_E_TABLE_FULL)) { c->big_image = 1; c->last_err_bits = 0; continue; }
     if (bits) return map_err_bits(bits);
-    newd = c->h_pinned[0]; added = c->h_pinned[1];
+    newd = (c->h_pinned + HP_COUNTERS)[CNT_NEWD]; added = (c->h_pinned + HP_COUNTERS)[CNT_ADDED];
     break;
   }
   HIPCHK(hipMemsetAsync(c->tab[c->cur ^ 1], 0, c->table_bytes, c->stream));
@@ -2778,10 +2850,10 @@ extern "C" int shk_unitig_set_write(shk_unitig_set *u, uint32_t k, const char *o
         if ((hp[i] & 15) == SHK_STOP_CIRCLE) fprintf(stderr, "SHK_UG_DEBUG circle id %u state %d keep %u len %u hmin %016llx\n", i, hs[i], hkeep[i], hl[i], (unsigned long long)hh[i]);
     }
     if (run_scan<uint32_t>(c, c, d_keep, n, nullptr, d_newid, d_sums) || run_scan<uint32_t>(c, c, d_lens, n, nullptr, d_off, d_sums)) { rc = SHK_ERR_HIP; break; }
-    if (hipMemcpyAsync(c->h_pinned + 45, d_newid + n, 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-        hipMemcpyAsync(c->h_pinned + 46, d_off + n, 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+    if (hipMemcpyAsync(c->h_pinned + HP_TOTAL, d_newid + n, 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+        hipMemcpyAsync(c->h_pinned + HP_AUX, d_off + n, 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
         hipStreamSynchronize(c->stream) != hipSuccess) { rc = SHK_ERR_HIP; break; }
-    nunits = c->h_pinned[45]; total = c->h_pinned[46];
+    nunits = c->h_pinned[HP_TOTAL]; total = c->h_pinned[HP_AUX];
     if (nunits == 0) break;
     if (dmalloc(&d_bases, total + 16) || dmalloc(&d_cnt, total + 16) || dmalloc(&d_uoff, nunits + 1) || dmalloc(&d_ulen, nunits + 1) ||
         dmalloc(&d_ul1, nunits + 1) || dmalloc(&d_med, nunits + 1) || dmalloc(&d_links, nunits * 8 + 8)) { rc = SHK_ERR_HIP; break; }

@@ -585,12 +585,10 @@ def hash_and_exchange(ctx, text, offs, lens, hb, world, rank, device, on_device=
     t0 = time.perf_counter()
     rc, nw, routed = 0, 0, None
     try:
-        if offs and not os.environ.get("SHK_NO_ROLL"):
+        if offs:
             # one pass over the text: every k-mer hashed and sent straight to its owner's bin of the send buffer
             dp, sc, nw = ctx.hash_route_chunks(text, offs, lens, world, on_device=on_device, text_bytes=text_bytes)
             routed = (dp, sc)
-        elif offs:
-            _, nw = ctx.hash_chunks(text, offs, lens, on_device=on_device, text_bytes=text_bytes)
     except ShkError as e:
         rc = e.code
     t1 = time.perf_counter()
