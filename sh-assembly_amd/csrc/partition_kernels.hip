@@ -7,6 +7,7 @@
 // (cqf_kernels.hip). Order inside a region is irrelevant: the filter's bytes depend only
 // on the key multiset.
 #include "shk_device.h"
+#include <type_traits>
 
 #define SHK_RP_TILE 4096     // keys per window
 #define SHK_RP_MAXP 1024     // at most 10 digit bits per level
@@ -19,6 +20,7 @@ struct ShkRpLevel {
   uint32_t hb;
   uint64_t q_lo;      // first quotient this context owns (multi-GPU shards)
   uint64_t nslots;    // quotients this context owns
+  uint32_t cb;        // chunk bits of the narrow record between the level in front of the last one and the last one (below)
   uint32_t out32;     // 1 (last level): write 32-bit records (quotient in region << 8 | remainder) << SHK_CHUNK_BITS | chunk
   uint32_t ablate;    // diagnostics only (SHK_RP_ABLATE): 1 = no reservation atomics, all windows write the same few KB per digit (results invalid)
   uint32_t slot_cap;  // last level only, 0 = off: bucket (region) i owns the fixed slot [i * slot_cap, (i + 1) * slot_cap) of the
@@ -35,6 +37,19 @@ struct ShkRpLevel {
 __device__ __forceinline__ uint32_t shk_word_region(uint64_t w, uint32_t hb, uint64_t q_lo) {
   uint64_t key = hb >= 64 ? w : (w & ((1ULL << hb) - 1));
   return (uint32_t)(((key >> 8) - q_lo) >> SHK_REGION_LOG2);
+}
+
+// The narrow record: what the level in front of the last one hands to the last one when the call's chunk tags fit cb =
+// 32 - 16 - (last level's digit bits) bits. Behind all levels but the last a word's bucket is its region's high digits, so
+//   rec32 = ((last digit << 16 | quotient in region << 8 | remainder) << cb) | chunk
+// is all that anybody still reads of it: half the bytes of the key word. (The digit and the quotient in the region are
+// adjacent bits of the quotient: the upper field is the low 16 + b_last bits of key - (q_lo << 8).)
+enum { RP_WORDS = 0, RP_NARROW_OUT = 1, RP_NARROW_IN = 2 };   // k_rp_scatter: 8-byte words in and out (the last level: 4-byte
+                                                              // records out); writes the narrow record; reads it
+__device__ __forceinline__ uint32_t shk_narrow_rec(uint64_t w, uint32_t hb, uint64_t q_lo, uint32_t cb) {
+  const uint64_t key = hb >= 64 ? w : (w & ((1ULL << hb) - 1));
+  const uint32_t up = (uint32_t)(key - (q_lo << 8)) & ((1u << (32 - cb)) - 1);
+  return (up << cb) | ((uint32_t)(w >> hb) & ((1u << cb) - 1));
 }
 
 // ---------------------------------------------------------------- exclusive scan (3 kernels)
@@ -110,9 +125,13 @@ __global__ void k_rp_tile_first(const uint64_t *bucket_base, uint32_t nbuckets, 
 // Histogram of the next digit. One workgroup takes `wtiles` consecutive windows, so that the global
 // counters of a (bucket, digit) see one atomic per workgroup and bucket, not one per window
 // (at the first level every window would hit the same P addresses).
-__global__ void k_rp_hist(const uint64_t *words, const uint64_t *n_p, const uint64_t *bucket_base,
+// NARROW: the input is the narrow record (the exact redo of a slotted last level behind a narrow level).
+template <bool NARROW>
+__global__ void k_rp_hist(const uint64_t *words_, const uint64_t *n_p, const uint64_t *bucket_base,
                           const uint32_t *tfb, ShkRpLevel lv, uint64_t *hist, uint32_t wtiles) {
   __shared__ uint32_t lh[SHK_RP_MAXP];
+  using W = typename std::conditional<NARROW, uint32_t, uint64_t>::type;
+  const W *words = reinterpret_cast<const W *>(words_);
   const uint64_t n = *n_p;
   const uint64_t wstart = (uint64_t)blockIdx.x * wtiles * SHK_RP_TILE;
   if (wstart >= n) return;
@@ -126,7 +145,7 @@ __global__ void k_rp_hist(const uint64_t *words, const uint64_t *n_p, const uint
     __syncthreads();
     // four loads in flight per thread
     for (uint64_t i0 = lo; i0 < hi; i0 += 4ull * blockDim.x) {
-      uint64_t w[4];
+      W w[4];
 #pragma unroll
       for (int u = 0; u < 4; u++) {
         const uint64_t i = i0 + (uint64_t)u * blockDim.x + threadIdx.x;
@@ -136,7 +155,7 @@ __global__ void k_rp_hist(const uint64_t *words, const uint64_t *n_p, const uint
       for (int u = 0; u < 4; u++) {
         const uint64_t i = i0 + (uint64_t)u * blockDim.x + threadIdx.x;
         if (i < hi) {
-          const uint32_t dg = (shk_word_region(w[u], lv.hb, lv.q_lo) >> lv.shift) & (P - 1);
+          const uint32_t dg = NARROW ? (uint32_t)(w[u] >> (16 + lv.cb)) : (shk_word_region(w[u], lv.hb, lv.q_lo) >> lv.shift) & (P - 1);
           const uint32_t grp = (uint32_t)(i >> SHK_RP_TILE0_LOG2) & ((1u << lv.ng_log2) - 1);     // the (first-level) scatter window this key lies in
           atomicAdd(&lh[(dg << lv.ng_log2) | grp], 1u);
         }
@@ -212,17 +231,23 @@ __global__ void k_rp_slot_cursors(uint64_t *cursor, uint64_t n, uint32_t cap) {
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) cursor[i] = i * cap;
 }
 
-template <int TILE_LOG2, int THREADS, int PMAX = SHK_RP_MAXP>
-__global__ void __launch_bounds__(THREADS) k_rp_scatter(const uint64_t *in, uint64_t *out, const uint64_t *n_p,
+// FORM (RP_WORDS, RP_NARROW_OUT, RP_NARROW_IN): which of `in` and `out` holds narrow records. A narrow record is made
+// from the key word as it is loaded (the last place the whole key exists: the SHK_E_CORRUPT check of a narrow batch is
+// here), so that the registers and the LDS stage of those instantiations hold 4 bytes per key.
+template <int TILE_LOG2, int THREADS, int PMAX = SHK_RP_MAXP, int FORM = RP_WORDS>
+__global__ void __launch_bounds__(THREADS) k_rp_scatter(const uint64_t *in_, uint64_t *out, const uint64_t *n_p,
                                                         const uint64_t *bucket_base, const uint32_t *tfb, ShkRpLevel lv,
                                                         uint64_t *cursor, uint32_t *err) {
   constexpr uint32_t SHK_RP_TILE_ = 1u << TILE_LOG2;
   constexpr int KPT_ = (int)(SHK_RP_TILE_ / THREADS);   // keys per thread (registers)
   static_assert(SHK_RP_TILE_ <= 65536, "a rank inside a digit takes 16 bits");
+  using WIN = typename std::conditional<FORM == RP_NARROW_IN, uint32_t, uint64_t>::type;    // what is loaded
+  using WST = typename std::conditional<FORM == RP_WORDS, uint64_t, uint32_t>::type;        // what is held and staged
+  const WIN *in = reinterpret_cast<const WIN *>(in_);
   __shared__ uint32_t lh[PMAX];      // digit counts (= next rank while counting); PMAX >= 2^lv.bits (the host's choice)
   __shared__ uint32_t lbase[PMAX];   // local exclusive base of each digit
   __shared__ uint64_t gbase[PMAX];   // reserved global base of each digit
-  __shared__ uint64_t stage[SHK_RP_TILE_];
+  __shared__ WST stage[SHK_RP_TILE_];
   __shared__ uint32_t scratch[SHK_MAX_WAVES + 1];
   const uint64_t n = *n_p;
   const uint64_t wstart = (uint64_t)blockIdx.x * SHK_RP_TILE_;
@@ -236,7 +261,7 @@ __global__ void __launch_bounds__(THREADS) k_rp_scatter(const uint64_t *in, uint
     if (hi <= lo) continue;
     const uint32_t cnt = (uint32_t)(hi - lo);
     for (uint32_t d = threadIdx.x; d < P; d += THREADS) lh[d] = 0;
-    uint64_t w[KPT_];
+    WIN w[KPT_];
 #pragma unroll
     for (int u = 0; u < KPT_; u++) {
       const uint32_t i = threadIdx.x + (uint32_t)u * THREADS;
@@ -244,12 +269,21 @@ __global__ void __launch_bounds__(THREADS) k_rp_scatter(const uint64_t *in, uint
     }
     __syncthreads();
     uint32_t dr[KPT_];               // digit << 16 | rank inside the digit (rank < SHK_RP_TILE)
+    WST x[KPT_];                     // the key as it is staged
 #pragma unroll
     for (int u = 0; u < KPT_; u++) {
       const uint32_t i = threadIdx.x + (uint32_t)u * THREADS;
       dr[u] = 0;
+      x[u] = (WST)w[u];
       if (i < cnt) {
-        const uint32_t d = (shk_word_region(w[u], lv.hb, lv.q_lo) >> lv.shift) & (P - 1);
+        uint32_t d;
+        if (FORM == RP_NARROW_IN) d = (uint32_t)(w[u] >> (16 + lv.cb));
+        else d = (shk_word_region(w[u], lv.hb, lv.q_lo) >> lv.shift) & (P - 1);
+        if (FORM == RP_NARROW_OUT) {
+          const uint64_t key = lv.hb >= 64 ? w[u] : (w[u] & ((1ULL << lv.hb) - 1));
+          if ((key >> 8) - lv.q_lo >= lv.nslots) atomicOr(err, SHK_E_CORRUPT);
+          x[u] = (WST)shk_narrow_rec(w[u], lv.hb, lv.q_lo, lv.cb);
+        }
         dr[u] = (d << 16) | atomicAdd(&lh[d], 1u);
       }
     }
@@ -275,23 +309,44 @@ __global__ void __launch_bounds__(THREADS) k_rp_scatter(const uint64_t *in, uint
 #pragma unroll
     for (int u = 0; u < KPT_; u++) {
       const uint32_t i = threadIdx.x + (uint32_t)u * THREADS;
-      if (i < cnt) stage[lbase[dr[u] >> 16] + (dr[u] & 0xFFFFu)] = w[u];
+      if (i < cnt) stage[lbase[dr[u] >> 16] + (dr[u] & 0xFFFFu)] = x[u];
     }
     __syncthreads();
-    for (uint32_t i = threadIdx.x; i < cnt; i += THREADS) {
-      uint64_t x = stage[i];
-      uint32_t d = (shk_word_region(x, lv.hb, lv.q_lo) >> lv.shift) & (P - 1);
-      if (lv.out32) {
-        // behind the last level a word's region is its bucket: the rebuild kernel only needs the
-        // quotient inside the region, the remainder and the chunk -- half the bytes, no 64-bit arithmetic
-        const uint64_t key = lv.hb >= 64 ? x : (x & ((1ULL << lv.hb) - 1));
-        const uint64_t q = (key >> 8) - lv.q_lo;
-        if (q >= lv.nslots) atomicOr(err, SHK_E_CORRUPT);
-        const uint32_t rec = ((((uint32_t)q & (SHK_REGION - 1)) << 8 | (uint32_t)(key & 0xff)) << SHK_CHUNK_BITS) |
-                             ((uint32_t)(x >> lv.hb) & (SHK_MAX_CHUNKS - 1));
-        if (gbase[d] != ~0ULL) reinterpret_cast<uint32_t *>(out)[gbase[d] + (i - lbase[d])] = rec;
-      } else {
-        out[gbase[d] + (i - lbase[d])] = x;
+    if (FORM == RP_NARROW_OUT) {
+      // the staged record no longer holds this level's digit: a wave takes whole digit runs (lh[] still holds their lengths).
+      // This trades balance for not keeping the digit: a run that is no multiple of 64 records leaves lanes idle (hash
+      // values: 128 runs of ~128 records over 16 waves here), and a batch whose keys crowd into one digit is written by one
+      // wave. Staging dr >> 16 next to the record would restore the flat loop for 1-2 more bytes of LDS per key.
+      uint32_t *out32 = reinterpret_cast<uint32_t *>(out);
+      for (uint32_t d = threadIdx.x / SHK_WAVE; d < P; d += THREADS / SHK_WAVE) {
+        const uint32_t l0 = lbase[d], len = lh[d];
+        const uint64_t g0 = gbase[d];
+        for (uint32_t j = threadIdx.x % SHK_WAVE; j < len; j += SHK_WAVE) out32[g0 + j] = stage[l0 + j];
+      }
+    } else {
+      for (uint32_t i = threadIdx.x; i < cnt; i += THREADS) {
+        const WST xs = stage[i];
+        if (FORM == RP_NARROW_IN) {
+          // the record the rebuild reads, bit for bit the one the 8-byte path writes below
+          const uint32_t d = xs >> (16 + lv.cb);
+          const uint32_t rec = (((uint32_t)(xs >> lv.cb) & 0xFFFFu) << SHK_CHUNK_BITS) | ((uint32_t)xs & ((1u << lv.cb) - 1));
+          if (gbase[d] != ~0ULL) reinterpret_cast<uint32_t *>(out)[gbase[d] + (i - lbase[d])] = rec;
+          continue;
+        }
+        const uint64_t x64 = xs;
+        uint32_t d = (shk_word_region(x64, lv.hb, lv.q_lo) >> lv.shift) & (P - 1);
+        if (lv.out32) {
+          // behind the last level a word's region is its bucket: the rebuild kernel only needs the
+          // quotient inside the region, the remainder and the chunk -- half the bytes, no 64-bit arithmetic
+          const uint64_t key = lv.hb >= 64 ? x64 : (x64 & ((1ULL << lv.hb) - 1));
+          const uint64_t q = (key >> 8) - lv.q_lo;
+          if (q >= lv.nslots) atomicOr(err, SHK_E_CORRUPT);
+          const uint32_t rec = ((((uint32_t)q & (SHK_REGION - 1)) << 8 | (uint32_t)(key & 0xff)) << SHK_CHUNK_BITS) |
+                               ((uint32_t)(x64 >> lv.hb) & (SHK_MAX_CHUNKS - 1));
+          if (gbase[d] != ~0ULL) reinterpret_cast<uint32_t *>(out)[gbase[d] + (i - lbase[d])] = rec;
+        } else {
+          out[gbase[d] + (i - lbase[d])] = x64;
+        }
       }
     }
     shk_lds_barrier();             // (LDS only: the runs just written drain to HBM behind it)

@@ -28,12 +28,12 @@
 
 enum {
   KP_COUNT_LINES, KP_SCAN_CHUNKS, KP_EMIT_READS, KP_COUNT_KEYS, KP_HASH, KP_SCAN, KP_RP_PREP, KP_RP_HIST,
-  KP_RP_SCATTER, KP_MERGE_SUM, KP_REGION_SCAN, KP_MERGE_WRITE, KP_MERGE_SPILL, KP_PLACE, KP_MARKS, KP_LOOKUP, KP_WALK, KP_UG_WALK, KP_UG_FINISH, KP_MERGE_FUSED, KP_MERGE_SAMPLE, KP_MISC, KP_ROLL_HIST, KP_ROLL_SCATTER, KP_PACK, KP_RP_SLOTS, KP_N
+  KP_RP_SCATTER, KP_MERGE_SUM, KP_REGION_SCAN, KP_MERGE_WRITE, KP_MERGE_SPILL, KP_PLACE, KP_MARKS, KP_LOOKUP, KP_WALK, KP_UG_WALK, KP_UG_FINISH, KP_MERGE_FUSED, KP_MERGE_SAMPLE, KP_MISC, KP_ROLL_HIST, KP_ROLL_SCATTER, KP_PACK, KP_RP_SLOTS, KP_RP_SCATTER_NARROW, KP_N
 };
 static const char *kp_names[KP_N] = {
   "k_count_lines", "k_scan_chunks", "k_emit_reads", "k_count_keys", "k_hash_reads", "k_scan_*", "k_rp_prep",
   "k_rp_hist", "k_rp_scatter", "k_region_merge<summary>", "k_region_scan", "k_region_merge<write>",
-  "k_region_merge<spill>", "k_region_place", "k_denoise_marks", "k_lookup", "k_extend_forward+k_select_seeds", "k_ug_walk", "k_ug_check/emit/median/links", "k_region_merge<fused>", "k_region_merge<sample>", "misc", "k_roll_hist", "k_roll_scatter", "k_pack_reads", "k_rp_slot_cursors"};
+  "k_region_merge<spill>", "k_region_place", "k_denoise_marks", "k_lookup", "k_extend_forward+k_select_seeds", "k_ug_walk", "k_ug_check/emit/median/links", "k_region_merge<fused>", "k_region_merge<sample>", "misc", "k_roll_hist", "k_roll_scatter", "k_pack_reads", "k_rp_slot_cursors", "k_rp_scatter<narrow>"};
 
 struct PendingEvent { int id; hipEvent_t a, b; };
 
@@ -84,6 +84,8 @@ struct ShkPartLevel {
   uint8_t scatter;     // k_rp_scatter instantiation
   bool pair_hist;      // when this level's words arrive unsorted, its counting pass also counts the next level (k_rp_hist2)
   bool may_slot;       // the last level, of index >= 1, with 4-byte output: region slots instead of a counting pass
+  bool may_narrow;     // the k_rp_scatter level in front of the last one: it may hand the last level 4-byte records
+                       // (partition_kernels.hip: the narrow record) when the batch's chunk tags fit ShkRpLevel::cb bits
 };
 
 // What a front end (parse, hash or roll, partition) works in: its stream, every buffer it writes, the state of its
@@ -335,7 +337,7 @@ static int create_init(shk_ctx *c, const shk_config *cfg) {
       uint32_t bits = (left + (c->nlevels - l) - 1) / (c->nlevels - l);
       left -= bits;
       c->lv[l].shift = left; c->lv[l].bits = bits; c->lv[l].nbuckets = nb; c->lv[l].hb = cfg->hb; c->lv[l].q_lo = c->q_lo;
-      c->lv[l].nslots = c->nslots; c->lv[l].out32 = 0; c->lv[l].ablate = 0; c->lv[l].ng_log2 = 0; c->lv[l].slot_cap = 0;
+      c->lv[l].nslots = c->nslots; c->lv[l].cb = 0; c->lv[l].out32 = 0; c->lv[l].ablate = 0; c->lv[l].ng_log2 = 0; c->lv[l].slot_cap = 0;
       nb <<= bits;
     }
     c->lv[c->nlevels - 1].out32 = 1;
@@ -346,6 +348,7 @@ static int create_init(shk_ctx *c, const shk_config *cfg) {
   if (c->threads < 64 || c->threads > 1024 || (c->threads & (c->threads - 1))) return SHK_ERR_ARG;
   c->hash_groups = cfg->hash_groups ? cfg->hash_groups : 2048;
   // the partition plan
+  const bool words8 = getenv("SHK_RP_WORDS8") && atoi(getenv("SHK_RP_WORDS8")) != 0;
   c->roll_two = c->nlevels >= 2 && c->lv[0].bits + c->lv[1].bits <= 14;   // two levels' digits fit one pass's LDS bins
   for (uint32_t l = 0; l < c->nlevels; l++) {
     const bool last = l + 1 == c->nlevels;
@@ -354,6 +357,9 @@ static int create_init(shk_ctx *c, const shk_config *cfg) {
     c->part[l].scatter = l == 0 && c->lv[0].ng_log2 ? RP_SCATTER_GROUPED : c->threads >= 512 && !last && c->lv[l].bits <= 8 ? RP_SCATTER_WIDE : RP_SCATTER_TILE;
     c->part[l].pair_hist = l == 0 && c->roll_two && c->lv[1].ng_log2 == 0;
     c->part[l].may_slot = last && l >= 1 && c->lv[l].out32;
+    // (level 0 of a context with two levels or more is the roll kernels'; SHK_RP_WORDS8=1: 8-byte words between all levels)
+    c->part[l].may_narrow = l >= 1 && l + 2 == c->nlevels && !words8;
+    c->lv[l].cb = 32 - 16 - c->lv[c->nlevels - 1].bits;
   }
   c->rounds_left = cfg->num_denoise;
   c->max_reads = cfg->max_batch_reads ? cfg->max_batch_reads : cfg->max_batch_bytes / 16 + 1024;
@@ -647,15 +653,16 @@ struct ShkPartInput {
   int in_buf;            // which d_words[] src[0] occupies; -1: neither
   uint32_t first_level;  // 1: src[0] is partitioned by the first digit already and d_base[1] holds the bucket bases
   bool counted[2];       // counted[l]: the producer has filled d_hist[l]
+  uint32_t nchunks;      // the words' chunk fields are chunk tags below this; 0: not known (or the field is a multiplicity)
 };
 // roll_stage: d_words[0] sorted by the first digit; the second level is counted when the two levels' digits fit one pass
-static ShkPartInput part_from_roll(const shk_ctx *c, const ShkStageBufs *b, uint64_t n) { return {{b->d_words[0], nullptr}, {n, 0}, 1, 0, 1, {false, c->roll_two}}; }
+static ShkPartInput part_from_roll(const shk_ctx *c, const ShkStageBufs *b, uint64_t n, uint32_t nchunks) { return {{b->d_words[0], nullptr}, {n, 0}, 1, 0, 1, {false, c->roll_two}, nchunks}; }
 // hash_stage with hist0: d_words[0] in emission order, the first level counted
-static ShkPartInput part_from_hash(const ShkStageBufs *b, uint64_t n) { return {{b->d_words[0], nullptr}, {n, 0}, 1, 0, 0, {true, false}}; }
+static ShkPartInput part_from_hash(const ShkStageBufs *b, uint64_t n, uint32_t nchunks) { return {{b->d_words[0], nullptr}, {n, 0}, 1, 0, 0, {true, false}, nchunks}; }
 // the caller's words, read in place (no staging copy), in one of the context's own buffers or not. w2: a second source
 // (shk_stage_words_pair: both are counted into one histogram and scattered with one set of cursors)
 static ShkPartInput part_from_words(const ShkStageBufs *b, const uint64_t *w, uint64_t n, const uint64_t *w2 = nullptr, uint64_t n2 = 0) {
-  return {{w, w2}, {n, n2}, w2 ? 2 : 1, w == b->d_words[0] ? 0 : w == b->d_words[1] ? 1 : -1, 0, {false, false}};
+  return {{w, w2}, {n, n2}, w2 ? 2 : 1, w == b->d_words[0] ? 0 : w == b->d_words[1] ? 1 : -1, 0, {false, false}, 0};
 }
 
 // Last level: fixed-capacity region slots instead of a histogram pass over the keys + scan, when the output buffer
@@ -679,10 +686,14 @@ static int partition_stage(const shk_ctx *c, ShkStageBufs *b, const ShkPartInput
   const uint32_t nwin = (uint32_t)(nmax / SHK_RP_TILE + 1);
   int cur = in.in_buf < 0 ? 1 : in.in_buf;   // the buffer the level's input occupies (neither: write to d_words[0] first)
   bool counted[4] = {in.counted[0], in.counted[1], false, false};
+  bool narrow = false;   // the level in hand writes narrow records
   b->region_cap = 0;
   for (uint32_t l = in.first_level; l < c->nlevels; l++) {
     const ShkPartLevel &pl = c->part[l];
     const uint64_t nb = c->lv[l].nbuckets, P = 1ULL << c->lv[l].bits;
+    // 4-byte records between this level and the next: the plan allows it and every chunk tag of the call fits
+    const bool narrow_in = narrow;
+    narrow = pl.may_narrow && in.nchunks && in.nchunks <= (1u << c->lv[l].cb);
     // the sources of this level: (words, their number on the device, their bucket bases, their number on the host)
     struct Src { const uint64_t *w, *n_p, *base; uint64_t n; } srcs[2] = {{l == in.first_level ? in.src[0] : b->d_words[cur], n_p, b->d_base[l], nmax}, {}};
     int nsrc = 1;
@@ -722,8 +733,12 @@ static int partition_stage(const shk_ctx *c, ShkStageBufs *b, const ShkPartInput
           ProfScope ps(c, b, KP_RP_HIST);
           const uint32_t wt = nwin / 4096 + 1;   // windows per workgroup
           for (int si = 0; si < nsrc; si++)
-            hipLaunchKernelGGL(k_rp_hist, dim3(nwin / wt + 1), dim3(c->threads), 0, b->stream, srcs[si].w, srcs[si].n_p, srcs[si].base, b->d_tfb, c->lv[l],
-                               b->d_hist[l], wt);
+            if (narrow_in)
+              hipLaunchKernelGGL(k_rp_hist<true>, dim3(nwin / wt + 1), dim3(c->threads), 0, b->stream, srcs[si].w, srcs[si].n_p, srcs[si].base, b->d_tfb,
+                                 c->lv[l], b->d_hist[l], wt);
+            else
+              hipLaunchKernelGGL(k_rp_hist<false>, dim3(nwin / wt + 1), dim3(c->threads), 0, b->stream, srcs[si].w, srcs[si].n_p, srcs[si].base, b->d_tfb,
+                                 c->lv[l], b->d_hist[l], wt);
         }
         // bases
         if (c->lv[l].ng_log2) {
@@ -739,11 +754,20 @@ static int partition_stage(const shk_ctx *c, ShkStageBufs *b, const ShkPartInput
         }
       }
       // scatter
-      { ProfScope ps(c, b, KP_RP_SCATTER);
+      { ProfScope ps(c, b, narrow || narrow_in ? KP_RP_SCATTER_NARROW : KP_RP_SCATTER);
         for (int si = 0; si < nsrc; si++) {
           const Src &S = srcs[si];
           const dim3 wide((uint32_t)(S.n >> SHK_RP_TILE0_LOG2) + 1);
-          if (pl.scatter == RP_SCATTER_GROUPED)      // (window groups are defined on the first level's 16384-key windows: SHK_RP_TILE0_LOG2)
+          if (narrow && pl.scatter == RP_SCATTER_WIDE)
+            hipLaunchKernelGGL((k_rp_scatter<SHK_RP_TILE0_LOG2, 1024, 256, RP_NARROW_OUT>), wide, dim3(1024), 0, b->stream, S.w, b->d_words[cur ^ 1], S.n_p,
+                               S.base, b->d_tfb, lvl, cursor, b->d_err);
+          else if (narrow)
+            hipLaunchKernelGGL((k_rp_scatter<12, SHK_RP_THREADS, SHK_RP_MAXP, RP_NARROW_OUT>), dim3((uint32_t)(S.n / SHK_RP_TILE + 1)), dim3(SHK_RP_THREADS), 0,
+                               b->stream, S.w, b->d_words[cur ^ 1], S.n_p, S.base, b->d_tfb, lvl, cursor, b->d_err);
+          else if (narrow_in)
+            hipLaunchKernelGGL((k_rp_scatter<12, SHK_RP_THREADS, SHK_RP_MAXP, RP_NARROW_IN>), dim3((uint32_t)(S.n / SHK_RP_TILE + 1)), dim3(SHK_RP_THREADS), 0,
+                               b->stream, S.w, b->d_words[cur ^ 1], S.n_p, S.base, b->d_tfb, lvl, cursor, b->d_err);
+          else if (pl.scatter == RP_SCATTER_GROUPED)      // (window groups are defined on the first level's 16384-key windows: SHK_RP_TILE0_LOG2)
             hipLaunchKernelGGL((k_rp_scatter<SHK_RP_TILE0_LOG2, 1024>), wide, dim3(1024), 0, b->stream, S.w, b->d_words[cur ^ 1], S.n_p, S.base,
                                b->d_tfb, lvl, cursor, b->d_err);
           else if (pl.scatter == RP_SCATTER_WIDE)
@@ -1436,7 +1460,7 @@ static int front_end(const shk_ctx *c, ShkStageBufs *b, const void *text, int on
   if (bits) return map_err_bits(bits);
   *nwords = b->h_pinned[HP_NWORDS];
   if (*nwords > c->cfg.max_batch_keys) return SHK_ERR_BATCH;
-  rc = partition_stage(c, b, roll ? part_from_roll(c, b, *nwords) : part_from_hash(b, *nwords), dst);
+  rc = partition_stage(c, b, roll ? part_from_roll(c, b, *nwords, nchunks) : part_from_hash(b, *nwords, nchunks), dst);
   *region_cap = b->region_cap;
   return rc;
 }
@@ -1712,7 +1736,7 @@ extern "C" int shk_route_words(shk_ctx *c, uint64_t nwords, uint32_t nshards, ui
   // one partition level over the WHOLE filter's regions: digit = owner
   ShkRpLevel lv;
   lv.shift = (c->cfg.qb - SHK_REGION_LOG2) - lg; lv.bits = lg; lv.nbuckets = 1; lv.hb = c->cfg.hb; lv.q_lo = 0;
-  lv.nslots = ~0ULL; lv.out32 = 0; lv.ablate = 0; lv.ng_log2 = 0; lv.slot_cap = 0;
+  lv.nslots = ~0ULL; lv.cb = 0; lv.out32 = 0; lv.ablate = 0; lv.ng_log2 = 0; lv.slot_cap = 0;
   if (set_nwords(c, nwords)) return SHK_ERR_HIP;
   const uint64_t *n_p = c->d_scalars + DS_NWORDS;
   const uint32_t nwin = (uint32_t)(nwords / SHK_RP_TILE + 1);
@@ -1723,7 +1747,7 @@ extern "C" int shk_route_words(shk_ctx *c, uint64_t nwords, uint32_t nshards, ui
   int rc = owner_bins(c, nshards, 1, [&] {
     ProfScope ps(c, KP_RP_HIST);
     const uint32_t wt = nwin / 4096 + 1;
-    hipLaunchKernelGGL(k_rp_hist, dim3(nwin / wt + 1), dim3(c->threads), 0, c->stream, c->d_words[0], n_p, c->d_base[0], c->d_tfb, lv, c->d_block_sums + ROUTE_HIST, wt);
+    hipLaunchKernelGGL(k_rp_hist<false>, dim3(nwin / wt + 1), dim3(c->threads), 0, c->stream, c->d_words[0], n_p, c->d_base[0], c->d_tfb, lv, c->d_block_sums + ROUTE_HIST, wt);
   }, counts, base);
   if (rc) return finish(c, rc);
   { ProfScope ps(c, KP_RP_SCATTER);
