@@ -28,6 +28,10 @@
  *   shk_dump              qf_iterator / qfi_get / qfi_next / qfi_end        cqf/gqf.c:2474-2601
  *   shk_merge             qf_merge                                          cqf/gqf.c:2614-2655
  *   shk_multi_merge       qf_multi_merge                                    cqf/gqf.c:2660-2704
+ *   shk_inner_product     qf_inner_product                                  cqf/gqf.c:2707-2733
+ *   shk_intersect         qf_intersect                                      cqf/gqf.c:2736-2757
+ *   shk_magnitude         qf_magnitude                                      cqf/gqf.c:2760-2763
+ *   shk_spectrum          (no counterpart: the reference's README sends the user to an outside program for F0, F1, f1, f2, ...)
  *   shk_import_shards     (no counterpart: the reference is one process) quotient-range shards -> the single table
  *   shk_stats             runtime->nelts / ndistinct_elts / num_deNoise    cqf/CQF_mt.h:277-288
  *   shk_destroy           CQF_mt::~CQF_mt -> qf_destroy                    cqf/CQF_mt.h:547-557; gqf.c:2306
@@ -286,6 +290,38 @@ int shk_merge(shk_ctx *dst, shk_ctx *src, shk_batch_stats *stats);
 int shk_multi_merge(shk_ctx *dst, shk_ctx *const *srcs, uint32_t n, shk_batch_stats *stats);
 int shk_import_shards(shk_ctx *ctx, const void *const *shard_blocks, const uint64_t *shard_bytes, uint32_t nshards,
                       int on_device, uint64_t nelts, uint64_t ndistinct);
+
+/* ---- analytics on resident tables. Readers: like shk_export_blocks they may first launch the pending placement of their
+ * operands. They work on a shard context too, over that shard's own quotients and overflow tail: the shards' histograms,
+ * totals and inner products add up to the whole filter's (max_count: take the maximum). Traveled bits are ignored.
+ * shk_spectrum: the abundance spectrum of the table. hist[i] (i < nbins-1) = entries whose count is i+1; hist[nbins-1] =
+ *   entries whose count is >= nbins. hist is a host pointer unless on_device != 0; hist may be NULL with nbins 0 (totals
+ *   only). After an error the content of hist is undefined. With F0 = distinct, F1 = total, f1 = hist[0], f2 = hist[1] the
+ *   reference README's recipe reads N = F1, n = F0 - f1 - f2, e = 1 - ((F1 - f1 - 2 f2) / F1)^(1/k).
+ * shk_inner_product: sum over the keys present in both of count_a * count_b, mod 2^64 (the reference accumulates in uint64_t).
+ *   a and b must agree in qb, hb, shard_index, num_shards and device (SHK_ERR_ARG otherwise: the reference's different-sizes
+ *   case is not supported); a == b is allowed. For two filters of equal size the reference ITERATES its second operand and
+ *   looks each key up in the first (gqf.c:2714-2722), and its qfi_next ends the iteration when it steps inside a run onto a
+ *   slot behind nslots (see shk_dump). ref_iterator_end != 0 reproduces that: entries of b at or behind its early-end point
+ *   do not contribute, while the lookups into a see everything; apart from this the product is symmetric.
+ *   ref_iterator_end == 0: every entry. An empty operand gives 0.
+ * shk_magnitude: (uint64_t)sqrt((double)inner_product(ctx, ctx)) -- the reference's expression, gqf.c:2762.
+ * shk_intersect: dst := the canonical table of { (key, count_b) : key in a and key in b } -- what qf_intersect(a, b, dst)
+ *   inserts into an empty dst: the iterated operand b gives the counts (swap the arguments to keep a's). dst's former
+ *   content is discarded, its traveled bits are zero; dst == a or dst == b is SHK_ERR_ARG, geometry as above. With
+ *   ref_iterator_end != 0 b's entries behind the early end are left out. An empty operand gives an empty table.
+ *   stats->kmers = sum of the counts written, stats->new_distinct = entries written; shk_stats(dst) reports the same as
+ *   nelts and ndistinct. A corrupt source table is SHK_ERR_CORRUPT with nothing written. */
+typedef struct shk_spectrum_totals {
+  uint64_t distinct;   /* F0: entries */
+  uint64_t total;      /* F1: sum of counts */
+  uint64_t sumsq;      /* sum of count^2 mod 2^64 (= inner product of the filter with itself) */
+  uint64_t max_count;  /* largest count present, 0 for an empty table */
+} shk_spectrum_totals;
+int shk_spectrum(shk_ctx *ctx, uint64_t *hist, uint32_t nbins, int on_device, shk_spectrum_totals *out);
+int shk_inner_product(shk_ctx *a, shk_ctx *b, int ref_iterator_end, uint64_t *out);
+int shk_magnitude(shk_ctx *ctx, int ref_iterator_end, uint64_t *out);
+int shk_intersect(shk_ctx *dst, shk_ctx *a, shk_ctx *b, int ref_iterator_end, shk_batch_stats *stats);
 
 int shk_stats(shk_ctx *ctx, shk_totals *out);
 /* 128-byte quotient_filter_metadata image (gqf.h:62-77) for this context */

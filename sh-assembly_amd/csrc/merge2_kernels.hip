@@ -1,6 +1,8 @@
 // Filter-to-filter kernels: the GPU form of the reference's iterator and merge utilities
 //   qf_iterator / qfi_get / qfi_next          cqf/gqf.c:2474-2601  -> k_region_dump
 //   qf_merge / qf_multi_merge                 cqf/gqf.c:2614-2704  -> k_region_merge2
+//   qf_inner_product / qf_intersect           cqf/gqf.c:2707-2757  -> k_region_join (+ k_region_iter_end)
+//   (the abundance spectrum of a table: no counterpart)           -> k_region_spectrum
 // and of the stitch of quotient-range shards into one table, which is the same
 // rebuild with a different second source.
 //
@@ -24,6 +26,7 @@ struct ShkSrc2 {
   uint64_t nblocks;                   // blocks of one source table
   uint32_t regions_per_src;
   uint32_t nsrc;
+  const unsigned long long *stop;     // joins only (null = none): entries of the FIRST table with key >= *stop take no part
 };
 
 // A region of one table, staged and indexed (lives in LDS).
@@ -163,10 +166,14 @@ __device__ __forceinline__ void shk_walk2(const ShkRegionView<IMGB> &V1, const S
   }
 }
 
+// One region of a table rebuilt from the walk of two (the body of k_region_merge2 and of k_region_join's two layout modes).
 // WRITE = false: run lengths -> (T, c) + statistics into the summary (then k_region_scan_*).
-// WRITE = true : lay the merged runs out from the free pointers in finB and store table B.
-template <bool WRITE, int IMGB>
-__global__ void __launch_bounds__(SHK_WAVE) k_region_merge2(ShkMergeArgs A, ShkSrc2 S) {
+// WRITE = true : lay the runs out from the free pointers in finB and store table B.
+// JOIN = false : every entry of either table, counts of equal keys added; statistics = keys new to table 1, occurrences of table 2.
+// JOIN = true  : the entries present in BOTH tables, with table 1's count (table 1 is the iterated operand of qf_intersect,
+//                gqf.c:2750-2756), those of table 1 at or behind *S.stop left out; statistics = entries and occurrences written.
+template <bool WRITE, int IMGB, bool JOIN>
+__device__ __forceinline__ void shk_region_rebuild2(const ShkMergeArgs &A, const ShkSrc2 &S) {
   constexpr unsigned IMG_SLOTS = IMGB * 64, IMG_BYTES = IMGB * SHK_BLOCK_BYTES;
   __shared__ ShkRegionView<IMGB> V1, V2;
   __shared__ __attribute__((aligned(16))) uint8_t nimg[IMG_BYTES + 16];
@@ -191,6 +198,12 @@ __global__ void __launch_bounds__(SHK_WAVE) k_region_merge2(ShkMergeArgs A, ShkS
   constexpr uint32_t per = SHK_REGION / SHK_WAVE;
   const uint32_t qa = tid * per;
   const bool active = ok && qa < nq;
+  // which entries of the walk the new table holds, and with what count
+  const uint64_t stop = (JOIN && S.stop) ? (uint64_t)*S.stop : ~0ULL;
+  auto kept = [&](uint32_t q, uint32_t rem, uint64_t total, bool in1, uint64_t c2, uint64_t *cnt) {
+    *cnt = JOIN ? total - c2 : total;
+    return !JOIN || (in1 && c2 != 0 && (((q0 + q) << 8) | rem) < stop);
+  };
   // ---- lengths
   ShkMP mine; mine.a = 0; mine.b = SHK_NEG_INF;
   uint32_t my_new = 0;
@@ -205,10 +218,12 @@ __global__ void __launch_bounds__(SHK_WAVE) k_region_merge2(ShkMergeArgs A, ShkS
       }
     };
     shk_walk2<IMGB>(V1, V2, qa, per, active, [&](uint32_t q, uint32_t rem, uint64_t total, bool in1, uint64_t c2, uint32_t, bool) {
+      uint64_t cnt;
+      if (!kept(q, rem, total, in1, c2, &cnt)) return;
       if (q != curq) { close_run(); curq = q; len = 0; }
-      len += shk_enc_len(rem, total);
-      if (!in1) my_new++;
-      my_added += c2;
+      len += shk_enc_len(rem, cnt);
+      if (JOIN || !in1) my_new++;
+      my_added += JOIN ? cnt : c2;
     });
     close_run();
   }
@@ -279,10 +294,12 @@ __global__ void __launch_bounds__(SHK_WAVE) k_region_merge2(ShkMergeArgs A, ShkS
         atomicOr(&nimg32[oo >> 2], 1u << (((oo & 3) << 3) + (curq & 7)));
       }
     };
-    shk_walk2<IMGB>(V1, V2, qa, per, active, [&](uint32_t q, uint32_t rem, uint64_t total, bool, uint64_t, uint32_t, bool) {
+    shk_walk2<IMGB>(V1, V2, qa, per, active, [&](uint32_t q, uint32_t rem, uint64_t total, bool in1, uint64_t c2, uint32_t, bool) {
+      uint64_t cnt;
+      if (!kept(q, rem, total, in1, c2, &cnt)) return;
       if (q != curq) { close_run(); curq = q; wp = rstart[q - qa]; }
       uint8_t enc[12];
-      const unsigned n = shk_enc_write(enc, rem, total);
+      const unsigned n = shk_enc_write(enc, rem, cnt);
       for (unsigned i = 0; i < n; i++) nimg[shk_img_slot_off(wp + i)] = enc[i];
       wp += n;
     });
@@ -290,6 +307,11 @@ __global__ void __launch_bounds__(SHK_WAVE) k_region_merge2(ShkMergeArgs A, ShkS
   }
   __syncthreads();
   shk_store_image<IMGB>(A, r, nregions, nimg, tid, nown, b0, q0, out_lo, out_hi, new_any, fout_rel);
+}
+
+template <bool WRITE, int IMGB>
+__global__ void __launch_bounds__(SHK_WAVE) k_region_merge2(ShkMergeArgs A, ShkSrc2 S) {
+  shk_region_rebuild2<WRITE, IMGB, false>(A, S);
 }
 
 // (key, count) of every entry in iterator order. PASS 0: entries per region -> nper[r]. PASS 1: write them at
@@ -323,6 +345,124 @@ __global__ void __launch_bounds__(SHK_WAVE) k_region_dump(ShkMergeArgs A, uint32
     if (stop && !first && q0 + pos > A.nslots) atomicMin(stop, (unsigned long long)o);
     o++;
   });
+}
+
+// ---- read-side analytics: the abundance spectrum of one table, and the joins of two (qf_inner_product, qf_intersect)
+
+template <typename T>
+__device__ __forceinline__ T shk_wave_max(T x) {
+  for (int d = 1; d < SHK_WAVE; d <<= 1) { const T y = __shfl_xor(x, d); x = y > x ? y : x; }
+  return x;
+}
+
+#define SHK_SPEC_LDS_BINS 256   // bins a workgroup keeps in LDS (counts 1 .. 256); larger counts, the rare tail, go to the global bins
+enum { SHK_SPEC_DISTINCT, SHK_SPEC_TOTAL, SHK_SPEC_SUMSQ, SHK_SPEC_MAX, SHK_SPEC_WORDS };   // totals[] = shk_spectrum_totals
+
+// hist[i] (i < nbins - 1) += entries whose count is i + 1, hist[nbins - 1] += entries whose count is >= nbins (nbins 0: totals
+// only). A workgroup (one wave) takes the regions blockIdx.x, blockIdx.x + gridDim.x, ...: per entry it updates one LDS bin and
+// its lanes' private totals; its non-zero bins and its wave-reduced totals reach global memory once, at its end. Integer
+// addition is associative, so the result does not depend on the order.
+template <int IMGB>
+__global__ void __launch_bounds__(SHK_WAVE) k_region_spectrum(ShkMergeArgs A, unsigned long long *hist, uint32_t nbins,
+                                                              unsigned long long *totals) {
+  __shared__ ShkRegionView<IMGB> V;
+  __shared__ unsigned long long bins[SHK_SPEC_LDS_BINS];
+  const unsigned tid = threadIdx.x;
+  const uint32_t nregions = (uint32_t)((A.nslots + SHK_REGION - 1) / SHK_REGION);
+  constexpr uint32_t per = SHK_REGION / SHK_WAVE;
+  const uint32_t qa = tid * per;
+  for (uint32_t i = tid; i < SHK_SPEC_LDS_BINS; i += SHK_WAVE) bins[i] = 0;
+  uint64_t distinct = 0, total = 0, sumsq = 0, maxc = 0;
+  for (uint32_t r = blockIdx.x; r < nregions; r += gridDim.x) {
+    const uint64_t q0 = (uint64_t)r * SHK_REGION;
+    const uint32_t nq = (uint32_t)((A.nslots - q0) < SHK_REGION ? (A.nslots - q0) : SHK_REGION);
+    const bool ok = shk_view_load<IMGB>(V, A.tabA, A.finA, r, nq, A.nblocks, tid, A.err);
+    ShkCur c;
+    shk_cur_init(c, V, qa, per, ok && qa < nq);
+    while (c.has) {
+      const uint64_t cnt = c.cnt;
+      distinct++; total += cnt; sumsq += cnt * cnt;
+      maxc = cnt > maxc ? cnt : maxc;
+      if (nbins) {
+        const uint32_t bin = cnt > nbins ? nbins - 1 : (uint32_t)(cnt - 1);
+        if (bin < SHK_SPEC_LDS_BINS) atomicAdd(&bins[bin], 1ULL);
+        else atomicAdd(&hist[bin], 1ULL);
+      }
+      shk_cur_next(c, V, qa);
+    }
+    __syncthreads();   // the next region's staging overwrites the view
+  }
+  for (uint32_t i = tid; i < SHK_SPEC_LDS_BINS && i < nbins; i += SHK_WAVE)
+    if (bins[i]) atomicAdd(&hist[i], bins[i]);
+  distinct = shk_wave_incl_add64(distinct);
+  total = shk_wave_incl_add64(total);
+  sumsq = shk_wave_incl_add64(sumsq);
+  maxc = shk_wave_max(maxc);
+  if (tid == SHK_WAVE - 1 && distinct) {
+    atomicAdd(&totals[SHK_SPEC_DISTINCT], (unsigned long long)distinct);
+    atomicAdd(&totals[SHK_SPEC_TOTAL], (unsigned long long)total);
+    atomicAdd(&totals[SHK_SPEC_SUMSQ], (unsigned long long)sumsq);
+    atomicMax(&totals[SHK_SPEC_MAX], (unsigned long long)maxc);
+  }
+}
+
+// Where the reference's iteration of the table ends early (see k_region_dump): *stop_key = the smallest key, relative to
+// this context's first quotient, of an entry that sits behind nslots without opening its run (~0 = no such entry: the
+// caller presets it). Launched over the last regions only, those whose image reaches behind nslots.
+template <int IMGB>
+__global__ void __launch_bounds__(SHK_WAVE) k_region_iter_end(ShkMergeArgs A, unsigned long long *stop_key) {
+  __shared__ ShkRegionView<IMGB> V;
+  const unsigned tid = threadIdx.x;
+  const uint32_t r = blockIdx.x + A.r0;
+  const uint64_t q0 = (uint64_t)r * SHK_REGION;
+  const uint32_t nq = (uint32_t)((A.nslots - q0) < SHK_REGION ? (A.nslots - q0) : SHK_REGION);
+  const bool ok = shk_view_load<IMGB>(V, A.tabA, A.finA, r, nq, A.nblocks, tid, A.err);
+  constexpr uint32_t per = SHK_REGION / SHK_WAVE;
+  const uint32_t qa = tid * per;
+  ShkCur c;
+  shk_cur_init(c, V, qa, per, ok && qa < nq);
+  while (c.has) {
+    if (!c.first && q0 + c.pos > A.nslots) {   // a lane's keys ascend: its first hit is its smallest
+      atomicMin(stop_key, (unsigned long long)(((q0 + c.q) << 8) | c.rem));
+      break;
+    }
+    shk_cur_next(c, V, qa);
+  }
+}
+
+// Two tables of one geometry walked together, table 1 (A.tabA) = the ITERATED operand of the reference (its qf_disk, the
+// second argument for equal sizes, gqf.c:2714-2722), table 2 (S.tab[0]) = the one it looks the keys up in.
+//   SHK_JOIN_DOT     *acc += sum over keys in both of count_1 * count_2, mod 2^64 (qf_inner_product, gqf.c:2723-2730).
+//                    Grid-stride over the regions like k_region_spectrum; lane-private products, one add per workgroup.
+//   SHK_JOIN_LENGTHS / SHK_JOIN_WRITE   the two launches that lay out the table of { (key, count_1) : key in both }
+//                    (qf_intersect, gqf.c:2750-2756), region = blockIdx.x + A.r0: shk_region_rebuild2 with JOIN set.
+// Entries of table 1 with key >= *S.stop (k_region_iter_end) take no part: the reference's iterator never reaches them.
+enum { SHK_JOIN_DOT, SHK_JOIN_LENGTHS, SHK_JOIN_WRITE };
+template <int MODE, int IMGB>
+__global__ void __launch_bounds__(SHK_WAVE) k_region_join(ShkMergeArgs A, ShkSrc2 S, unsigned long long *acc) {
+  if constexpr (MODE != SHK_JOIN_DOT) {
+    shk_region_rebuild2<MODE == SHK_JOIN_WRITE, IMGB, true>(A, S);
+  } else {
+    __shared__ ShkRegionView<IMGB> V1, V2;
+    const unsigned tid = threadIdx.x;
+    const uint32_t nregions = (uint32_t)((A.nslots + SHK_REGION - 1) / SHK_REGION);
+    constexpr uint32_t per = SHK_REGION / SHK_WAVE;
+    const uint32_t qa = tid * per;
+    const uint64_t stop = S.stop ? (uint64_t)*S.stop : ~0ULL;
+    uint64_t dot = 0;
+    for (uint32_t r = blockIdx.x; r < nregions; r += gridDim.x) {
+      const uint64_t q0 = (uint64_t)r * SHK_REGION;
+      const uint32_t nq = (uint32_t)((A.nslots - q0) < SHK_REGION ? (A.nslots - q0) : SHK_REGION);
+      bool ok = shk_view_load<IMGB>(V1, A.tabA, A.finA, r, nq, A.nblocks, tid, A.err);
+      ok = shk_view_load<IMGB>(V2, S.tab[0], S.fin[0], r, nq, S.nblocks, tid, A.err) && ok;
+      shk_walk2<IMGB>(V1, V2, qa, per, ok && qa < nq, [&](uint32_t q, uint32_t rem, uint64_t total, bool in1, uint64_t c2, uint32_t, bool) {
+        if (in1 && c2 != 0 && (((q0 + q) << 8) | rem) < stop) dot += (total - c2) * c2;
+      });
+      __syncthreads();   // the next region's staging overwrites the views
+    }
+    dot = shk_wave_incl_add64(dot);
+    if (tid == SHK_WAVE - 1 && dot) atomicAdd(acc, (unsigned long long)dot);
+  }
 }
 
 // (key, count) pairs -> key words for the counted form of the rebuild: a pair becomes ceil(count / 4096) words whose

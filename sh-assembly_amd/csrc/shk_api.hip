@@ -28,12 +28,12 @@
 
 enum {
   KP_COUNT_LINES, KP_SCAN_CHUNKS, KP_EMIT_READS, KP_COUNT_KEYS, KP_HASH, KP_SCAN, KP_RP_PREP, KP_RP_HIST,
-  KP_RP_SCATTER, KP_MERGE_SUM, KP_REGION_SCAN, KP_MERGE_WRITE, KP_MERGE_SPILL, KP_PLACE, KP_MARKS, KP_LOOKUP, KP_WALK, KP_UG_WALK, KP_UG_FINISH, KP_MERGE_FUSED, KP_MERGE_SAMPLE, KP_MISC, KP_ROLL_HIST, KP_ROLL_SCATTER, KP_PACK, KP_RP_SLOTS, KP_RP_SCATTER_NARROW, KP_N
+  KP_RP_SCATTER, KP_MERGE_SUM, KP_REGION_SCAN, KP_MERGE_WRITE, KP_MERGE_SPILL, KP_PLACE, KP_MARKS, KP_LOOKUP, KP_WALK, KP_UG_WALK, KP_UG_FINISH, KP_MERGE_FUSED, KP_MERGE_SAMPLE, KP_MISC, KP_ROLL_HIST, KP_ROLL_SCATTER, KP_PACK, KP_RP_SLOTS, KP_RP_SCATTER_NARROW, KP_SPECTRUM, KP_JOIN, KP_N
 };
 static const char *kp_names[KP_N] = {
   "k_count_lines", "k_scan_chunks", "k_emit_reads", "k_count_keys", "k_hash_reads", "k_scan_*", "k_rp_prep",
   "k_rp_hist", "k_rp_scatter", "k_region_merge<summary>", "k_region_scan", "k_region_merge<write>",
-  "k_region_merge<spill>", "k_region_place", "k_denoise_marks", "k_lookup", "k_extend_forward+k_select_seeds", "k_ug_walk", "k_ug_check/emit/median/links", "k_region_merge<fused>", "k_region_merge<sample>", "misc", "k_roll_hist", "k_roll_scatter", "k_pack_reads", "k_rp_slot_cursors", "k_rp_scatter<narrow>"};
+  "k_region_merge<spill>", "k_region_place", "k_denoise_marks", "k_lookup", "k_extend_forward+k_select_seeds", "k_ug_walk", "k_ug_check/emit/median/links", "k_region_merge<fused>", "k_region_merge<sample>", "misc", "k_roll_hist", "k_roll_scatter", "k_pack_reads", "k_rp_slot_cursors", "k_rp_scatter<narrow>", "k_region_spectrum", "k_region_join"};
 
 struct PendingEvent { int id; hipEvent_t a, b; };
 
@@ -47,8 +47,11 @@ enum ShkDevSlot {
   DS_MARKS = 3,        // k_denoise_marks, k_denoise_marks_virtual: singletons the range walk protects
   DS_MAX_COUNT = 4,    // shk_insert_counted: largest count of the slice (k_expand_counted<0>)
   DS_DUMP_STOP = 5,    // shk_dump: where the reference's iterator would end
+  DS_JOIN_STOP = 6,    // shk_inner_product, shk_intersect: the key at which the reference's iteration of b ends (k_region_iter_end)
+  DS_JOIN_ACC = 7,     // shk_inner_product: the sum
   DS_WALK_IN = 8,      // point_walk: state of the range walk entering this shard, 2 words
   DS_WALK_OUT = 10,    // point_walk: ... and leaving it, 2 words
+  DS_SPECTRUM = 12,    // shk_spectrum: the totals, SHK_SPEC_WORDS = 4 words
   DS_STAMPS = 16,      // SHK_STAMPS diagnostics: 16 words of cycle counts (ShkMergeArgs::dbg)
   DS_PAIR_LEN = 40,    // shk_stage_words_pair: lengths of the two sources, 2 words
   DS_PAIR_BASE = 42,   // shk_stage_words_pair: their one-bucket base arrays {0, na} and {0, nb}, 2 + 2 words
@@ -57,13 +60,15 @@ enum ShkDevSlot {
 // The 64 words of the pinned mirror ShkStageBufs::h_pinned: what the host reads back, and small uploads' sources.
 enum ShkHostSlot {
   HP_COUNTERS = 0,     // merge_summary, point_read, merge2_run: d_counters, SHK_NCOUNTERS words (CNT_*, SHK_CNT_*)
+  HP_SPECTRUM = 8,     // shk_spectrum: DS_SPECTRUM read back, 4 words
   HP_ERR = 40,         // err_enqueue / err_take: the error word (4 bytes)
   HP_NREADS = 41,      // parse_stage: DS_NREADS read back
   HP_NWORDS = 42,      // front_end, shk_hash_chunks: DS_NWORDS read back
   HP_NWORDS_IN = 43,   // set_nwords: source of the upload to DS_NWORDS
   HP_FREE_PTR = 44,    // shk_stats: free pointer behind the last region
   HP_TOTAL = 45,       // shk_insert_counted: words of the slice; shk_dump: entries; unitig write: units
-  HP_AUX = 46,         // shk_insert_counted: DS_MAX_COUNT read back; shk_dump: DS_DUMP_STOP in and out; unitig write: total length
+  HP_AUX = 46,         // shk_insert_counted: DS_MAX_COUNT read back; shk_dump: DS_DUMP_STOP in and out; unitig write: total length;
+                       // shk_inner_product: DS_JOIN_ACC read back
   HP_MARKS = 47,       // point_walk: DS_MARKS read back
   HP_IFIN = 48,        // point_try: free pointer behind the intermediate table's last region
   HP_IFIRST = 49,      // point_try: first length byte of the intermediate table (quotient 0 has a run)
@@ -74,6 +79,7 @@ enum ShkHostSlot {
 };
 enum { CNT_NEWD, CNT_ADDED, CNT_REMOVED, CNT_ADDED_BEFORE };   // counters[0..3]: the statistics of a pass (ShkMergeArgs::counters)
 static_assert(HP_COUNTERS + SHK_NCOUNTERS <= HP_ERR, "the counters mirror ends before the error word");
+static_assert(HP_COUNTERS + SHK_NCOUNTERS <= HP_SPECTRUM && DS_SPECTRUM + (int)SHK_SPEC_WORDS <= DS_STAMPS, "the spectrum's totals have four words of their own");
 static_assert(DS_END <= SHK_SCALAR_WORDS && HP_END <= SHK_SCALAR_WORDS, "both blocks fit their 64 words");
 static_assert(DS_PAIR_BASE + 4 == DS_END && HP_PAIR + (DS_END - DS_PAIR_LEN) == HP_END, "the pair block is uploaded in one copy");
 
@@ -2300,20 +2306,50 @@ extern "C" int shk_dump(shk_ctx *c, uint64_t *keys, uint64_t *counts, uint64_t c
   return finish(c, 0);
 }
 
-// dst := canonical table of (dst's entries + the second source's entries), counts of equal keys added
-static int merge2_run(shk_ctx *c, const ShkSrc2 &S, uint64_t *newd_out, uint64_t *added_out) {
+// Where the reference's iteration of the table A.tabA ends early: *stop = the first key it does not reach, ~0 when it reaches
+// all. Only the regions whose image reaches behind nslots can hold such an entry.
+static int launch_iter_end(shk_ctx *c, ShkMergeArgs A, unsigned long long *stop) {
+  HIPCHK(hipMemsetAsync(stop, 0xFF, 8, c->stream));
+  const uint64_t img_slots = c->big_image ? SHK_IMG_BLOCKS_BIG * 64 : SHK_IMG_SLOTS;
+  A.r0 = c->nslots > img_slots ? (uint32_t)((c->nslots - img_slots) / SHK_REGION) : 0;
+  const uint32_t nblk = c->nregions - A.r0;
+  ProfScope ps(c, KP_JOIN);
+  if (c->big_image) hipLaunchKernelGGL((k_region_iter_end<SHK_IMG_BLOCKS_BIG>), dim3(nblk), dim3(SHK_WAVE), 0, c->stream, A, stop);
+  else hipLaunchKernelGGL((k_region_iter_end<SHK_IMG_BLOCKS>), dim3(nblk), dim3(SHK_WAVE), 0, c->stream, A, stop);
+  return SHK_OK;
+}
+
+template <bool WRITE>
+static void launch_rebuild2(shk_ctx *c, ShkMergeArgs &A, const ShkSrc2 &S, bool join) {
+  constexpr int JM = WRITE ? SHK_JOIN_WRITE : SHK_JOIN_LENGTHS;
+  unsigned long long *none = nullptr;
+  SHK_FOR_REGION_SLICES(c, A, nblk) {
+    if (join) {
+      if (c->big_image) hipLaunchKernelGGL((k_region_join<JM, SHK_IMG_BLOCKS_BIG>), dim3(nblk), dim3(SHK_WAVE), 0, c->stream, A, S, none);
+      else hipLaunchKernelGGL((k_region_join<JM, SHK_IMG_BLOCKS>), dim3(nblk), dim3(SHK_WAVE), 0, c->stream, A, S, none);
+    } else {
+      if (c->big_image) hipLaunchKernelGGL((k_region_merge2<WRITE, SHK_IMG_BLOCKS_BIG>), dim3(nblk), dim3(SHK_WAVE), 0, c->stream, A, S);
+      else hipLaunchKernelGGL((k_region_merge2<WRITE, SHK_IMG_BLOCKS>), dim3(nblk), dim3(SHK_WAVE), 0, c->stream, A, S);
+    }
+  }
+}
+
+// The two-launch layout of a table walked from two: table 1 = (tab1, fin1), table 2 = S; the result replaces c's table.
+// join = false (merge2_run): every entry of either, counts of equal keys added. join = true (intersect_run): the entries of
+// table 1 whose key table 2 holds too, with table 1's counts; S.stop != null: those behind the reference's early end take no
+// part. Nothing of c changes unless the lengths pass is clean.
+static int rebuild2_run(shk_ctx *c, const uint8_t *tab1, const uint64_t *fin1, const ShkSrc2 &S, bool join, uint64_t *newd_out,
+                        uint64_t *added_out) {
   ShkMergeArgs A;
   uint64_t newd = 0, added = 0;
-  { int rc = table_sync(c); if (rc) return rc; }
   for (int attempt = 0; attempt < 2; attempt++) {
     fill_args(c, &A, nullptr, 0, 0, 0);
+    A.tabA = tab1; A.finA = fin1;
     HIPCHK(hipMemsetAsync(c->d_counters, 0, (SHK_CNT_NOVER + 1) * 8, c->stream));
     c->spill_valid = 0;
+    if (join && S.stop) { int rc = launch_iter_end(c, A, (unsigned long long *)S.stop); if (rc) return rc; }
     { ProfScope ps(c, KP_MERGE_SUM);
-      SHK_FOR_REGION_SLICES(c, A, nblk) {
-        if (c->big_image) hipLaunchKernelGGL((k_region_merge2<false, SHK_IMG_BLOCKS_BIG>), dim3(nblk), dim3(SHK_WAVE), 0, c->stream, A, S);
-        else hipLaunchKernelGGL((k_region_merge2<false, SHK_IMG_BLOCKS>), dim3(nblk), dim3(SHK_WAVE), 0, c->stream, A, S);
-      } }
+      launch_rebuild2<false>(c, A, S, join); }
     { ProfScope ps(c, KP_REGION_SCAN);
       const uint32_t ntiles = (c->nregions + SHK_RSCAN_TILE - 1) / SHK_RSCAN_TILE;
       hipLaunchKernelGGL(k_region_scan_a, dim3(ntiles), dim3(c->threads), 0, c->stream, c->d_summary, c->nregions, c->d_tile_a, c->d_tile_b);
@@ -2331,15 +2367,22 @@ static int merge2_run(shk_ctx *c, const ShkSrc2 &S, uint64_t *newd_out, uint64_t
   }
   HIPCHK(hipMemsetAsync(c->tab[c->cur ^ 1], 0, c->table_bytes, c->stream));
   { ProfScope ps(c, KP_MERGE_WRITE);
-    SHK_FOR_REGION_SLICES(c, A, nblk) {
-      if (c->big_image) hipLaunchKernelGGL((k_region_merge2<true, SHK_IMG_BLOCKS_BIG>), dim3(nblk), dim3(SHK_WAVE), 0, c->stream, A, S);
-      else hipLaunchKernelGGL((k_region_merge2<true, SHK_IMG_BLOCKS>), dim3(nblk), dim3(SHK_WAVE), 0, c->stream, A, S);
-    } }
+    launch_rebuild2<true>(c, A, S, join); }
   HIPCHK(hipGetLastError());
   c->rec_live = 0; c->table_stale = 0;
   c->cur ^= 1;
   *newd_out = newd; *added_out = added;
   return SHK_OK;
+}
+
+// dst := canonical table of (dst's entries + the second source's entries), counts of equal keys added
+static int merge2_run(shk_ctx *c, const ShkSrc2 &S, uint64_t *newd_out, uint64_t *added_out) {
+  { int rc = table_sync(c); if (rc) return rc; }
+  return rebuild2_run(c, c->tab[c->cur], c->fin[c->cur], S, false, newd_out, added_out);
+}
+// dst := canonical table of { (key, count_b) : key in a and in b }; dst's own content is not read (nor its placement run)
+static int intersect_run(shk_ctx *dst, const shk_ctx *b, const ShkSrc2 &a, uint64_t *newd_out, uint64_t *added_out) {
+  return rebuild2_run(dst, b->tab[b->cur], b->fin[b->cur], a, true, newd_out, added_out);
 }
 
 extern "C" int shk_merge(shk_ctx *dst, shk_ctx *src, shk_batch_stats *stats) {
@@ -2373,6 +2416,121 @@ extern "C" int shk_multi_merge(shk_ctx *dst, shk_ctx *const *srcs, uint32_t n, s
   }
   if (stats) *stats = tot;
   return SHK_OK;
+}
+
+// ------------------------------------------------------------------ analytics on resident tables: spectrum, inner product, intersect
+// (qf_inner_product gqf.c:2707-2733, qf_intersect :2736-2757, qf_magnitude :2760-2763; the spectrum has no counterpart)
+
+static bool same_geometry(const shk_ctx *x, const shk_ctx *y) {
+  return x->dev == y->dev && x->cfg.qb == y->cfg.qb && x->cfg.hb == y->cfg.hb && x->q_lo == y->q_lo && x->nslots == y->nslots;
+}
+// the grid of the grid-stride analytics kernels: at most every wave slot of the device once (256 CUs x 32 one-wave workgroups
+// with the default hash_groups), so that a workgroup's one flush pays for many regions
+static uint32_t analytics_grid(const shk_ctx *c) {
+  const uint64_t cap = 4ull * c->hash_groups;
+  return (uint32_t)(c->nregions < cap ? c->nregions : cap);
+}
+
+extern "C" int shk_spectrum(shk_ctx *c, uint64_t *hist, uint32_t nbins, int on_device, shk_spectrum_totals *out) {
+  if (!c || (nbins && !hist) || (!nbins && !out)) return SHK_ERR_ARG;
+  HIPCHK(hipSetDevice(c->dev));
+  { int rc = table_sync(c); if (rc) return rc; }
+  ShkMergeArgs A;
+  fill_args(c, &A, nullptr, 0, 0, 0);
+  unsigned long long *dh = (unsigned long long *)hist, *dt = (unsigned long long *)(c->d_scalars + DS_SPECTRUM);
+  if (nbins && !on_device) { uint64_t *p = nullptr; if (dmalloc(&p, nbins)) return SHK_ERR_HIP; dh = (unsigned long long *)p; }
+  struct Free { void *p; ~Free() { if (p) hipFree(p); } } fr{(nbins && !on_device) ? dh : nullptr};
+  if (!nbins) dh = nullptr;
+  const uint32_t grid = analytics_grid(c);
+  for (int attempt = 0; attempt < 2; attempt++) {
+    if (nbins) HIPCHK(hipMemsetAsync(dh, 0, (uint64_t)nbins * 8, c->stream));
+    HIPCHK(hipMemsetAsync(dt, 0, SHK_SPEC_WORDS * 8, c->stream));
+    { ProfScope ps(c, KP_SPECTRUM);
+      if (c->big_image) hipLaunchKernelGGL((k_region_spectrum<SHK_IMG_BLOCKS_BIG>), dim3(grid), dim3(SHK_WAVE), 0, c->stream, A, dh, nbins, dt);
+      else hipLaunchKernelGGL((k_region_spectrum<SHK_IMG_BLOCKS>), dim3(grid), dim3(SHK_WAVE), 0, c->stream, A, dh, nbins, dt); }
+    HIPCHK(hipGetLastError());
+    uint32_t bits = 0;
+    if (fetch_err(c, &bits)) return SHK_ERR_HIP;
+    if ((bits & SHK_E_OLD_EXTENT) && !c->big_image) { c->big_image = 1; c->last_err_bits = 0; continue; }
+    if (bits) { prof_collect(c); return map_err_bits(bits); }
+    break;
+  }
+  HIPCHK(hipMemcpyAsync(c->h_pinned + HP_SPECTRUM, dt, SHK_SPEC_WORDS * 8, hipMemcpyDeviceToHost, c->stream));
+  if (nbins && !on_device) HIPCHK(hipMemcpyAsync(hist, dh, (uint64_t)nbins * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (out) {
+    const uint64_t *t = c->h_pinned + HP_SPECTRUM;
+    out->distinct = t[SHK_SPEC_DISTINCT]; out->total = t[SHK_SPEC_TOTAL]; out->sumsq = t[SHK_SPEC_SUMSQ]; out->max_count = t[SHK_SPEC_MAX];
+  }
+  return finish(c, 0);
+}
+
+// both operands' tables written and at rest (the join runs on the stream of the context that launches it)
+static int join_operands(shk_ctx *a, shk_ctx *b) {
+  { int rc = table_sync(a); if (rc) return rc; }
+  if (b != a) { int rc = table_sync(b); if (rc) return rc; }
+  HIPCHK(hipStreamSynchronize(a->stream));
+  if (b != a) HIPCHK(hipStreamSynchronize(b->stream));
+  return SHK_OK;
+}
+// a as the looked-up operand of a join launched by `run`
+static ShkSrc2 join_source(const shk_ctx *a, shk_ctx *run, int ref_iterator_end) {
+  ShkSrc2 S;
+  memset(&S, 0, sizeof(S));
+  S.tab[0] = a->tab[a->cur]; S.fin[0] = a->fin[a->cur]; S.nblocks = a->nblocks; S.regions_per_src = a->nregions; S.nsrc = 1;
+  S.stop = ref_iterator_end ? (const unsigned long long *)(run->d_scalars + DS_JOIN_STOP) : nullptr;
+  return S;
+}
+
+extern "C" int shk_inner_product(shk_ctx *a, shk_ctx *b, int ref_iterator_end, uint64_t *out) {
+  if (!a || !b || !out || !same_geometry(a, b)) return SHK_ERR_ARG;
+  HIPCHK(hipSetDevice(a->dev));
+  { int rc = join_operands(a, b); if (rc) return rc; }
+  const ShkSrc2 S = join_source(a, a, ref_iterator_end);
+  unsigned long long *acc = (unsigned long long *)(a->d_scalars + DS_JOIN_ACC);
+  const uint32_t grid = analytics_grid(a);
+  for (int attempt = 0; attempt < 2; attempt++) {
+    ShkMergeArgs A;
+    fill_args(a, &A, nullptr, 0, 0, 0);
+    A.tabA = b->tab[b->cur]; A.finA = b->fin[b->cur];     // the iterated operand
+    HIPCHK(hipMemsetAsync(acc, 0, 8, a->stream));
+    if (S.stop) { int rc = launch_iter_end(a, A, (unsigned long long *)S.stop); if (rc) return rc; }
+    { ProfScope ps(a, KP_JOIN);
+      if (a->big_image) hipLaunchKernelGGL((k_region_join<SHK_JOIN_DOT, SHK_IMG_BLOCKS_BIG>), dim3(grid), dim3(SHK_WAVE), 0, a->stream, A, S, acc);
+      else hipLaunchKernelGGL((k_region_join<SHK_JOIN_DOT, SHK_IMG_BLOCKS>), dim3(grid), dim3(SHK_WAVE), 0, a->stream, A, S, acc); }
+    HIPCHK(hipGetLastError());
+    uint32_t bits = 0;
+    if (fetch_err(a, &bits)) return SHK_ERR_HIP;
+    if ((bits & SHK_E_OLD_EXTENT) && !a->big_image) { a->big_image = 1; a->last_err_bits = 0; continue; }
+    if (bits) { prof_collect(a); return map_err_bits(bits); }
+    break;
+  }
+  HIPCHK(hipMemcpyAsync(a->h_pinned + HP_AUX, acc, 8, hipMemcpyDeviceToHost, a->stream));
+  HIPCHK(hipStreamSynchronize(a->stream));
+  *out = a->h_pinned[HP_AUX];
+  return finish(a, 0);
+}
+
+extern "C" int shk_magnitude(shk_ctx *c, int ref_iterator_end, uint64_t *out) {
+  if (!c || !out) return SHK_ERR_ARG;
+  uint64_t ip = 0;
+  int rc = shk_inner_product(c, c, ref_iterator_end, &ip);
+  if (rc) return rc;
+  *out = (uint64_t)sqrt((double)ip);
+  return SHK_OK;
+}
+
+extern "C" int shk_intersect(shk_ctx *dst, shk_ctx *a, shk_ctx *b, int ref_iterator_end, shk_batch_stats *stats) {
+  if (!dst || !a || !b || dst == a || dst == b || !same_geometry(dst, a) || !same_geometry(dst, b)) return SHK_ERR_ARG;
+  HIPCHK(hipSetDevice(dst->dev));
+  { int rc = join_operands(a, b); if (rc) return rc; }
+  uint64_t newd = 0, added = 0;
+  int rc = intersect_run(dst, b, join_source(a, dst, ref_iterator_end), &newd, &added);
+  if (!rc) {
+    dst->nelts = added; dst->ndistinct = newd;
+    if (stats) { memset(stats, 0, sizeof(*stats)); stats->kmers = added; stats->new_distinct = newd; }
+  }
+  return finish(dst, rc);
 }
 
 // The whole filter from its quotient-range shards: shard s (a table in the layout shk_export_blocks gives for a context

@@ -37,6 +37,13 @@ class Totals(C.Structure):
                 ("nblocks", C.c_uint64), ("table_bytes", C.c_uint64), ("free_pointer", C.c_uint64)]
 
 
+class SpectrumTotals(C.Structure):
+    _fields_ = [("distinct", C.c_uint64), ("total", C.c_uint64), ("sumsq", C.c_uint64), ("max_count", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class Summary(C.Structure):
     _fields_ = [("new_distinct", C.c_uint64), ("added", C.c_uint64), ("removed", C.c_uint64),
                 ("err_bits", C.c_uint32), ("reserved", C.c_uint32)]
@@ -67,7 +74,8 @@ EXPORTS = ["shk_create", "shk_destroy", "shk_count_chunks", "shk_hash_chunks", "
            "shk_unitigs_add_seeds", "shk_unitig_set_write", "shk_select_seeds", "shk_denoise",
            "shk_stats", "shk_header", "shk_export_blocks", "shk_export_cqf", "shk_import_cqf", "shk_import_blocks",
            "shk_lookup", "shk_profile_enable", "shk_profile_get", "shk_profile_reset", "shk_strerror",
-           "shk_last_error_bits", "shk_insert_counted", "shk_dump", "shk_merge", "shk_multi_merge", "shk_import_shards", "shk_table_ptr", "shk_unitigs_add_reads"]
+           "shk_last_error_bits", "shk_insert_counted", "shk_dump", "shk_merge", "shk_multi_merge", "shk_import_shards", "shk_table_ptr", "shk_unitigs_add_reads",
+           "shk_spectrum", "shk_inner_product", "shk_magnitude", "shk_intersect"]
 
 _libs = {}
 
@@ -121,6 +129,10 @@ def load(path=None):
     L.shk_multi_merge.argtypes = [vp, C.POINTER(vp), u32, C.POINTER(BatchStats)]
     L.shk_import_shards.argtypes = [vp, C.POINTER(vp), pu64, u32, i32, u64, u64]
     L.shk_table_ptr.argtypes = [vp, C.POINTER(vp), pu64]
+    L.shk_spectrum.argtypes = [vp, vp, u32, i32, C.POINTER(SpectrumTotals)]
+    L.shk_inner_product.argtypes = [vp, vp, i32, pu64]
+    L.shk_magnitude.argtypes = [vp, i32, pu64]
+    L.shk_intersect.argtypes = [vp, vp, vp, i32, C.POINTER(BatchStats)]
     L.shk_profile_enable.argtypes = [vp, i32]
     L.shk_profile_get.argtypes = [vp, C.POINTER(KernelTime), i32]
     L.shk_profile_reset.argtypes = [vp]
@@ -483,6 +495,39 @@ class Context:
         st = BatchStats()
         arr = (C.c_void_p * max(len(others), 1))(*[o.h for o in others])
         self._chk(self.L.shk_multi_merge(self.h, arr, len(others), C.byref(st)))
+        return st.as_dict()
+
+    def spectrum(self, nbins=256):
+        """(hist, totals): hist[i] = entries whose count is i + 1, the last bin takes every larger count; totals =
+        dict(distinct, total, sumsq, max_count). nbins = 0 (or None): totals only, hist = []"""
+        nbins = int(nbins or 0)
+        t = SpectrumTotals()
+        h = (C.c_uint64 * max(nbins, 1))()
+        self._chk(self.L.shk_spectrum(self.h, C.cast(h, C.c_void_p) if nbins else None, nbins, 0, C.byref(t)))
+        return [h[i] for i in range(nbins)], t.as_dict()
+
+    def spectrum_into(self, d_hist, nbins):
+        """the same with the histogram left on the device: d_hist = integer device pointer of nbins 64-bit words (they
+        are overwritten); returns the totals"""
+        t = SpectrumTotals()
+        self._chk(self.L.shk_spectrum(self.h, C.c_void_p(int(d_hist)), int(nbins), 1, C.byref(t)))
+        return t.as_dict()
+
+    def inner_product(self, other, ref_iterator_end=False):
+        """sum over common keys of count_self * count_other mod 2^64 (qf_inner_product(self, other): `other` is iterated)"""
+        v = C.c_uint64()
+        self._chk(self.L.shk_inner_product(self.h, other.h, 1 if ref_iterator_end else 0, C.byref(v)))
+        return v.value
+
+    def magnitude(self, ref_iterator_end=False):
+        v = C.c_uint64()
+        self._chk(self.L.shk_magnitude(self.h, 1 if ref_iterator_end else 0, C.byref(v)))
+        return v.value
+
+    def intersect_from(self, a, b, ref_iterator_end=False):
+        """self := { (key, count_b) : key in a and in b } (qf_intersect(a, b, self)); returns the statistics"""
+        st = BatchStats()
+        self._chk(self.L.shk_intersect(self.h, a.h, b.h, 1 if ref_iterator_end else 0, C.byref(st)))
         return st.as_dict()
 
     def import_shards(self, shard_blocks, nelts=0, ndistinct=0):

@@ -7,6 +7,8 @@ predict_build()     expected occupied slots chunk by chunk for the synthetic rea
                     t = 1 deNoise schedule (CQF_mt.h:837-869)
 plan_build()        the -N the bench passes: the exact number of k-mers it will present, with head room
                     added in 2 % steps until the predicted peak load is at most `max_load`
+params_from_spectrum()  the README's recipe for -N -n -e from an abundance spectrum (ntCard's F0, F1, f1, f2, ...
+                    there; Context.spectrum() of a built filter here)
 
 Why head room is needed at all: the reference's formula budgets `n * (enc + 1.5)` slots for the true
 k-mers and ONE slot per false k-mer between two rounds, and then lowers the number of rounds until the
@@ -227,3 +229,19 @@ def plan_build(K, G, L, err, kmers_per_chunk, nchunks, n_true=None, world=1, max
     return {"N": N, "n": n_true, "e": err, "qb": qb, "formula_rounds": nd0, "formula_trigger": trig0, "rounds": nd,
             "trigger": trigger, "predicted_peak_slots": int(p["peak_slots"]), "predicted_peak_load": load,
             "predicted_rounds_fired": p["rounds_fired"], "xnslots": xnslots(qb, world)}
+
+
+def params_from_spectrum(distinct, total, hist, k, false_max=2):
+    """(N, n, e) for the command line's -N -n -e by the reference README's recipe (README.md:88-93), from a spectrum:
+    distinct = F0, total = F1, hist[i] = number of distinct k-mers that occur i + 1 times (only hist[:false_max] is
+    read). K-mers with count <= false_max are taken as false (2 for deep data, 1 for shallow data, README.md:94):
+        N = F1    n = F0 - f1 - .. - f<false_max>    e = 1 - ((F1 - 1 f1 - .. - false_max f<false_max>) / F1)^(1/k)"""
+    if false_max < 0 or false_max > len(hist):
+        raise ValueError("the histogram must hold the bins 1 .. false_max")
+    if total <= 0 or k <= 0:
+        raise ValueError("an empty spectrum gives no parameters")
+    low = [int(x) for x in hist[:false_max]]
+    n = int(distinct) - sum(low)
+    true_total = int(total) - sum((i + 1) * f for i, f in enumerate(low))
+    e = 1.0 - (true_total / float(total)) ** (1.0 / k)
+    return int(total), n, e
