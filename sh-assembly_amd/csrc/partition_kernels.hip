@@ -26,7 +26,9 @@ struct ShkRpLevel {
   uint32_t slot_cap;  // last level only, 0 = off: bucket (region) i owns the fixed slot [i * slot_cap, (i + 1) * slot_cap) of the
                       // output instead of an exact range from a histogram pass + scan (the keys are hash values: a
                       // region's share of a batch is its mean +- a few sigma); `cursor` starts at the slots' first
-                      // positions and ends as the regions' END positions. A region that gets more raises SHK_E_SLOT_FULL
+                      // positions and ends as the regions' END positions. A region that gets more raises SHK_E_SLOT_FULL.
+                      // The level in front of the last one may be slotted the same way (narrow records out, the slots of a
+                      // batch whose first level came slotted out of k_roll_scatter); there the bit is SHK_E_SLOT_FULL_UP
   uint32_t ng_log2;   // first level only: every digit's bucket is laid out as 2^ng_log2 sub-buckets, one per window group
                       // (window index mod 2^ng_log2), each with its own cursor, so that the windows of a batch do not all
                       // reserve from the same P addresses. Measured on 832 M keys: the scatter itself is unchanged (its
@@ -126,8 +128,10 @@ __global__ void k_rp_tile_first(const uint64_t *bucket_base, uint32_t nbuckets, 
 // counters of a (bucket, digit) see one atomic per workgroup and bucket, not one per window
 // (at the first level every window would hit the same P addresses).
 // NARROW: the input is the narrow record (the exact redo of a slotted last level behind a narrow level).
+// Slotted input (here and in k_rp_scatter): bucket b is [bucket_base[b], bucket_end[b]) and a gap may follow it; *n_p is
+// then the input's EXTENT in positions (all slots), not the number of words. bucket_end null: bucket_base[b + 1].
 template <bool NARROW>
-__global__ void k_rp_hist(const uint64_t *words_, const uint64_t *n_p, const uint64_t *bucket_base,
+__global__ void k_rp_hist(const uint64_t *words_, const uint64_t *n_p, const uint64_t *bucket_base, const uint64_t *bucket_end,
                           const uint32_t *tfb, ShkRpLevel lv, uint64_t *hist, uint32_t wtiles) {
   __shared__ uint32_t lh[SHK_RP_MAXP];
   using W = typename std::conditional<NARROW, uint32_t, uint64_t>::type;
@@ -139,7 +143,8 @@ __global__ void k_rp_hist(const uint64_t *words_, const uint64_t *n_p, const uin
   const uint32_t P = 1u << lv.bits;
   for (uint32_t b = tfb[(uint64_t)blockIdx.x * wtiles]; b < lv.nbuckets && bucket_base[b] < wend; b++) {
     const uint64_t lo = bucket_base[b] > wstart ? bucket_base[b] : wstart;
-    const uint64_t hi = bucket_base[b + 1] < wend ? bucket_base[b + 1] : wend;
+    const uint64_t be = bucket_end ? bucket_end[b] : bucket_base[b + 1];
+    const uint64_t hi = be < wend ? be : wend;
     if (hi <= lo) continue;
     for (uint32_t d = threadIdx.x; d < (P << lv.ng_log2); d += blockDim.x) lh[d] = 0;
     __syncthreads();
@@ -230,14 +235,23 @@ __global__ void k_rp_slot_cursors(uint64_t *cursor, uint64_t n, uint32_t cap) {
   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) cursor[i] = i * cap;
 }
+// the slots of a level above the last one: the n buckets' bases (base[n] = all slots), their cursors, and the extent
+// in positions that the next level's windows cover
+__global__ void k_rp_slot_bases(uint64_t *base, uint64_t *cursor, uint64_t n, uint64_t cap, uint64_t *extent) {
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i <= n; i += stride) {
+    base[i] = i * cap;
+    if (i < n) cursor[i] = i * cap; else *extent = n * cap;
+  }
+}
 
 // FORM (RP_WORDS, RP_NARROW_OUT, RP_NARROW_IN): which of `in` and `out` holds narrow records. A narrow record is made
 // from the key word as it is loaded (the last place the whole key exists: the SHK_E_CORRUPT check of a narrow batch is
 // here), so that the registers and the LDS stage of those instantiations hold 4 bytes per key.
 template <int TILE_LOG2, int THREADS, int PMAX = SHK_RP_MAXP, int FORM = RP_WORDS>
 __global__ void __launch_bounds__(THREADS) k_rp_scatter(const uint64_t *in_, uint64_t *out, const uint64_t *n_p,
-                                                        const uint64_t *bucket_base, const uint32_t *tfb, ShkRpLevel lv,
-                                                        uint64_t *cursor, uint32_t *err) {
+                                                        const uint64_t *bucket_base, const uint64_t *bucket_end, const uint32_t *tfb,
+                                                        ShkRpLevel lv, uint64_t *cursor, uint32_t *err) {
   constexpr uint32_t SHK_RP_TILE_ = 1u << TILE_LOG2;
   constexpr int KPT_ = (int)(SHK_RP_TILE_ / THREADS);   // keys per thread (registers)
   static_assert(SHK_RP_TILE_ <= 65536, "a rank inside a digit takes 16 bits");
@@ -257,7 +271,8 @@ __global__ void __launch_bounds__(THREADS) k_rp_scatter(const uint64_t *in_, uin
   // (tfb is indexed by 4096-key windows)
   for (uint32_t b = (lv.nbuckets > 1 ? tfb[(uint64_t)blockIdx.x << (TILE_LOG2 - 12)] : 0u); b < lv.nbuckets && bucket_base[b] < wend; b++) {
     const uint64_t lo = bucket_base[b] > wstart ? bucket_base[b] : wstart;
-    const uint64_t hi = bucket_base[b + 1] < wend ? bucket_base[b + 1] : wend;
+    const uint64_t be = bucket_end ? bucket_end[b] : bucket_base[b + 1];
+    const uint64_t hi = be < wend ? be : wend;
     if (hi <= lo) continue;
     const uint32_t cnt = (uint32_t)(hi - lo);
     for (uint32_t d = threadIdx.x; d < P; d += THREADS) lh[d] = 0;
@@ -299,7 +314,7 @@ __global__ void __launch_bounds__(THREADS) k_rp_scatter(const uint64_t *in_, uin
         if (lv.ablate & 1) gbase[d] = cursor[((uint64_t)b * P + d) << lv.ng_log2] + (uint64_t)(blockIdx.x % 1024) * 24;
         else gbase[d] = v ? atomicAdd((unsigned long long *)&cursor[((((uint64_t)b * P) + d) << lv.ng_log2) | (blockIdx.x & ((1u << lv.ng_log2) - 1))], (unsigned long long)v) : 0;
         if (lv.slot_cap && v && gbase[d] + v > ((uint64_t)b * P + d + 1) * lv.slot_cap) {
-          atomicOr(err, SHK_E_SLOT_FULL);
+          atomicOr(err, lv.out32 ? SHK_E_SLOT_FULL : SHK_E_SLOT_FULL_UP);
           gbase[d] = ~0ULL;              // (nothing of this run is written)
         }
       }
@@ -321,6 +336,7 @@ __global__ void __launch_bounds__(THREADS) k_rp_scatter(const uint64_t *in_, uin
       for (uint32_t d = threadIdx.x / SHK_WAVE; d < P; d += THREADS / SHK_WAVE) {
         const uint32_t l0 = lbase[d], len = lh[d];
         const uint64_t g0 = gbase[d];
+        if (g0 == ~0ULL) continue;     // (a slotted level: the run did not fit)
         for (uint32_t j = threadIdx.x % SHK_WAVE; j < len; j += SHK_WAVE) out32[g0 + j] = stage[l0 + j];
       }
     } else {

@@ -4,12 +4,19 @@
 // its two 64-lane XOR scans, 6.5 ms per 832 M k-mers) plus the first partition level (write 8 B, read 8 B, write 8 B per
 // key: k_rp_scatter, 2.7 ms) by ONE THREAD PER READ that restates reads_to_kmers (cqf/CQF_mt.h:610-731) literally --
 // the serial roll of base/nthash.hpp:305-309, the un-inspected first window, the restart behind an 'N' -- at about 30
-// vector operations per k-mer, twice:
-//   k_roll_hist      hashes every k-mer and counts the first-level digits (nothing is written but 128 counters);
-//   k_roll_scatter   hashes every k-mer again and sends it straight to its digit's bucket through the same LDS staging
-//                    the partition's scatter uses (16384-key windows, one LDS atomic per key for count and rank, digit
-//                    runs written contiguously).
-// Hashing twice costs less than one round trip of the keys through HBM. Order inside a bucket is free.
+// vector operations per k-mer:
+//   k_roll_scatter   hashes every k-mer and sends it straight to its digit's bucket through the same LDS staging the
+//                    partition's scatter uses (16384-key windows, one LDS atomic per key for count and rank, digit runs
+//                    written contiguously);
+//   k_roll_hist      in front of it, where the buckets need exact bases: hashes every k-mer too and counts the
+//                    first-level digits (nothing is written but the counters).
+// Where to put a bucket without counting it first: the keys are hash values, so a digit's share of a batch is its mean
+// plus or minus a few sigma, and every digit can own a slot of fixed capacity (the host's roll_keys, k_roll_slot_ends:
+// the mean share of the most keys the text can hold + 6 sigma). A three-level context runs a narrow batch
+// that way at all three levels and never launches k_roll_hist; a slot that overflows (repeats: one k-mer a million
+// times) raises SHK_E_SLOT_FULL_UP and the host hashes the batch again behind a histogram pass. Everything else
+// (two- and four-level contexts, shk_hash_route_chunks, batches of more chunks than the narrow record holds) hashes twice,
+// which still costs less than one round trip of the keys through HBM. Order inside a bucket is free.
 //
 // The roll in table form, T = the base's row (A, C, G, T; anything else = seed 0, nthash.hpp:120-153):
 //   fh' = rol1(fh) ^ rol(seed[out], k) ^ seed[in]            rh' = ror1(rh) ^ ror1(seedc[out]) ^ rol(seedc[in], k-1)
@@ -29,9 +36,9 @@ struct ShkRollArgs {
   uint32_t dig_shift, dig_bits;    // first partition level: digit = (region >> dig_shift) & (2^dig_bits - 1)
   uint32_t hist_shift, hist_bits;  // k_roll_hist: bin = (region >> hist_shift) & (2^hist_bits - 1)
   uint64_t *hist;                  // k_roll_hist: 2^hist_bits counters
-  uint64_t *cursor;                // k_roll_scatter: next free position of every digit's bucket (starts at its base)
+  uint64_t *cursor;                // k_roll_scatter: next free position of every digit's bucket (starts at its base, or at its slot's)
   uint64_t *out;
-  uint64_t cap;                    // words `out` holds
+  uint64_t cap;                    // words `out` holds (a slotted batch: all slots, see k_roll_slot_ends)
   uint32_t *err;
   // 2-bit staging (k_pack_reads), null = none: read r's bases, 64 per 16-byte unit, start at unit pk_base[r];
   // pk_flag[r] = its number of units (0 = too short or too long a read), bit 31 set = holds a byte that is no base
@@ -407,6 +414,7 @@ __global__ void __launch_bounds__(THREADS) k_roll_scatter(ShkRollArgs A) {
     // a thread whose read is used up takes its next one
     while (!have && r < nreads) {
       const uint64_t st = A.rd_start[r], en = A.rd_end[r];
+      if (en - st > 65535) atomicOr(A.err, SHK_E_BAD_FASTQ);                       // SHK_MAX_READ (a slotted batch has no histogram pass to say so)
       if (en - st <= 65535 && en - st >= A.k) {
         s.st = st; s.len = (uint32_t)(en - st); s.i = 0; s.fill = 0; s.fh = 0; s.rh = 0;
         tag = (uint64_t)(A.chunk_first + A.rd_chunk[r] * A.chunk_mul) << A.hb;
@@ -462,4 +470,25 @@ __global__ void __launch_bounds__(THREADS) k_roll_scatter(ShkRollArgs A) {
     shk_lds_barrier();
     if (!more) break;
   }
+}
+
+// behind a slotted k_roll_scatter: the digits' cursors are their buckets' ends; the number of key words is what they
+// advanced by. A cursor behind its slot's end = that digit got more than the slot holds: SHK_E_SLOT_FULL_UP. The
+// overflow is found HERE, from the cursors, and not at the reservation: k_roll_scatter<1024, 1> uses all of the 128
+// VGPRs its sixteen waves leave a lane, and the test there (a 64-bit product and compare next to the sixteen keys that
+// wait in registers) made it spill and cost 0.1 ms of its 3.6 per 832 M keys. An overflowing run has by then been
+// written past its slot into the next digit's (never past `cap` = all slots: the store's own bound) -- which nobody
+// reads, since the host hashes such a batch again behind a histogram pass. One workgroup.
+__global__ void k_roll_slot_ends(const uint64_t *cursor, uint32_t P, uint64_t cap, uint64_t *end, uint64_t *nwords, uint32_t *err) {
+  __shared__ uint64_t scratch[SHK_MAX_WAVES + 1];
+  uint64_t s = 0;
+  for (uint32_t d = threadIdx.x; d < P; d += blockDim.x) {
+    const uint64_t cu = cursor[d];
+    s += cu - (uint64_t)d * cap;
+    const bool over = cu > (uint64_t)(d + 1) * cap;
+    if (over) atomicOr(err, SHK_E_SLOT_FULL_UP);
+    end[d] = over ? (uint64_t)(d + 1) * cap : cu;
+  }
+  const uint64_t tot = shk_block_sum64(s, scratch);
+  if (threadIdx.x == 0) *nwords = tot;
 }

@@ -55,7 +55,9 @@ enum ShkDevSlot {
   DS_STAMPS = 16,      // SHK_STAMPS diagnostics: 16 words of cycle counts (ShkMergeArgs::dbg)
   DS_PAIR_LEN = 40,    // shk_stage_words_pair: lengths of the two sources, 2 words
   DS_PAIR_BASE = 42,   // shk_stage_words_pair: their one-bucket base arrays {0, na} and {0, nb}, 2 + 2 words
-  DS_END = 46
+  DS_EXTENT = 46,      // a batch with slotted upper levels: positions (all slots) of the roll kernels' output, word 0, and of the
+                       // middle level's, word 1 -- what the partition kernels take as their input's length in place of DS_NWORDS
+  DS_END = 48
 };
 // The 64 words of the pinned mirror ShkStageBufs::h_pinned: what the host reads back, and small uploads' sources.
 enum ShkHostSlot {
@@ -81,7 +83,7 @@ enum { CNT_NEWD, CNT_ADDED, CNT_REMOVED, CNT_ADDED_BEFORE };   // counters[0..3]
 static_assert(HP_COUNTERS + SHK_NCOUNTERS <= HP_ERR, "the counters mirror ends before the error word");
 static_assert(HP_COUNTERS + SHK_NCOUNTERS <= HP_SPECTRUM && DS_SPECTRUM + (int)SHK_SPEC_WORDS <= DS_STAMPS, "the spectrum's totals have four words of their own");
 static_assert(DS_END <= SHK_SCALAR_WORDS && HP_END <= SHK_SCALAR_WORDS, "both blocks fit their 64 words");
-static_assert(DS_PAIR_BASE + 4 == DS_END && HP_PAIR + (DS_END - DS_PAIR_LEN) == HP_END, "the pair block is uploaded in one copy");
+static_assert(DS_PAIR_BASE + 4 == DS_EXTENT && HP_PAIR + (DS_EXTENT - DS_PAIR_LEN) == HP_END, "the pair block is uploaded in one copy");
 
 // How a partition level runs, fixed by the geometry (create_init); a batch adds what its producer has counted already
 // (ShkPartInput::counted) and whether region slots are worth trying (slot_capacity).
@@ -114,6 +116,7 @@ struct ShkStageBufs {
   uint64_t *d_base_sub = nullptr;         // first level with window groups: scanned bases of the (digit, group) sub-buckets
   uint64_t *d_base[5] = {};               // base[l]: bucket bases entering level l (base[nlevels] = region_base)
   uint64_t *d_cursor = nullptr;
+  uint64_t *d_end[3] = {};                // end[l], l = 1, 2: ends of the slotted buckets entering level l (contexts whose plan has roll_slots)
   uint32_t *d_tfb = nullptr;
   uint32_t *d_err = nullptr;
   uint64_t *h_pinned = nullptr;           // [SHK_SCALAR_WORDS] pinned, see ShkHostSlot
@@ -122,6 +125,10 @@ struct ShkStageBufs {
                                 // [r * region_cap, ...) and d_base[nlevels][r] is its END (ShkRpLevel::slot_cap)
   uint32_t slot_overflows = 0;  // consecutive batches whose slotted last level overflowed; at 2 the slots are switched off
   int slots_off = 0;
+  uint64_t roll_cap = 0;        // the batch in hand: 0 = roll_stage left exact bucket bases; else digit d owns the slot [d * roll_cap, ...)
+                                // of d_words[0] and d_end[1][d] is its end (k_roll_slot_ends)
+  uint32_t up_overflows = 0;    // consecutive batches whose slotted upper levels overflowed (SHK_E_SLOT_FULL_UP); at 2 they are
+  int up_off = 0;               // switched off. Apart from slot_overflows, which counts the last level's
   // profiling
   double prof_ms[KP_N] = {};
   uint64_t prof_n[KP_N] = {};
@@ -140,6 +147,7 @@ struct shk_ctx : ShkStageBufs {
   ShkRpLevel lv[4];
   ShkPartLevel part[4];         // the partition plan, level by level
   bool roll_two;                // roll_stage's histogram pass counts the first two levels' digits together (they fit its LDS bins)
+  bool roll_slots;              // three levels, all slotted: a narrow batch of text runs without any counting pass (roll_stage)
   uint32_t threads, hash_groups;
   // state
   uint64_t nelts, ndistinct;
@@ -259,6 +267,10 @@ static uint64_t level_out(const shk_ctx *c, uint32_t l) { return (uint64_t)c->lv
 
 // The stream and the buffers of one front end, sized from the context's geometry. lent: the overlapped front end, whose
 // two words buffers and last-level bases are its slots' (set batch by batch; not allocated and not freed here).
+// words of every buffer that can be d_words[]: slotted upper levels need room for a full batch plus the slots' slack
+// (128 slots of a 6.5 M share: 837.5 M words for 832 M keys)
+static uint64_t words_cap(const shk_ctx *c) { return c->cfg.max_batch_keys + (c->roll_slots ? c->cfg.max_batch_keys / 64 : 0); }
+
 static int bufs_alloc(const shk_ctx *c, ShkStageBufs *b, bool lent) {
   const uint64_t capk = c->cfg.max_batch_keys;
   const uint32_t maxch = SHK_MAX_CHUNKS;
@@ -272,7 +284,7 @@ static int bufs_alloc(const shk_ctx *c, ShkStageBufs *b, bool lent) {
       dmalloc(&b->d_reads_base, maxch + 1)) return SHK_ERR_HIP;
   if (dmalloc(&b->d_rd_start, c->max_reads + 1) || dmalloc(&b->d_rd_end, c->max_reads + 1) ||
       dmalloc(&b->d_nkeys, c->max_reads + 1) || dmalloc(&b->d_rd_chunk, c->max_reads + 1) || dmalloc(&b->d_key_base, c->max_reads + 2)) return SHK_ERR_HIP;
-  if (!lent && (dmalloc(&b->d_words[0], capk + 1) || dmalloc(&b->d_words[1], capk + 1))) return SHK_ERR_HIP;
+  if (!lent && (dmalloc(&b->d_words[0], words_cap(c) + 1) || dmalloc(&b->d_words[1], words_cap(c) + 1))) return SHK_ERR_HIP;
   if (dmalloc(&b->d_scalars, SHK_SCALAR_WORDS)) return SHK_ERR_HIP;
   HIPCHK(hipMemsetAsync(b->d_scalars, 0, SHK_SCALAR_WORDS * 8, b->stream));
   {
@@ -290,7 +302,9 @@ static int bufs_alloc(const shk_ctx *c, ShkStageBufs *b, bool lent) {
   }
   { const uint64_t nb = level_out(c, c->nlevels - 1), first = 1ULL << (c->lv[0].bits + c->lv[0].ng_log2);
     if (dmalloc(&b->d_cursor, (nb > first ? nb : first) + 2)) return SHK_ERR_HIP; }
-  if (dmalloc(&b->d_tfb, capk / SHK_RP_TILE + 2)) return SHK_ERR_HIP;
+  // (windows of 4096 positions; a slotted middle level's output is up to two 4-byte records per word of its buffer)
+  if (dmalloc(&b->d_tfb, (c->roll_slots ? 2 * words_cap(c) : capk) / SHK_RP_TILE + 2)) return SHK_ERR_HIP;
+  if (c->roll_slots && (dmalloc(&b->d_end[1], level_out(c, 0) + 2) || dmalloc(&b->d_end[2], level_out(c, 1) + 2))) return SHK_ERR_HIP;
   if (dmalloc(&b->d_err, 4)) return SHK_ERR_HIP;
   HIPCHK(hipMemsetAsync(b->d_err, 0, 16, b->stream));
   HIPCHK(hipHostMalloc((void **)&b->h_pinned, SHK_SCALAR_WORDS * sizeof(uint64_t), hipHostMallocDefault));
@@ -306,7 +320,7 @@ static void bufs_free(const shk_ctx *c, ShkStageBufs *b) {
   b->evpool.clear();
   hipFree(b->d_text); hipFree(b->d_chunk_off); hipFree(b->d_chunk_len); hipFree(b->d_nlines); hipFree(b->d_reads_base);
   hipFree(b->d_rd_start); hipFree(b->d_rd_end); hipFree(b->d_rd_chunk); hipFree(b->d_nkeys); hipFree(b->d_key_base); hipFree(b->d_scalars);
-  hipFree(b->d_block_sums); hipFree(b->d_base_sub); hipFree(b->d_cursor); hipFree(b->d_tfb); hipFree(b->d_err);
+  hipFree(b->d_block_sums); hipFree(b->d_base_sub); hipFree(b->d_cursor); hipFree(b->d_end[1]); hipFree(b->d_end[2]); hipFree(b->d_tfb); hipFree(b->d_err);
   if (!b->lent) { hipFree(b->d_words[0]); hipFree(b->d_words[1]); }
   for (uint32_t l = 0; l < 4; l++) hipFree(b->d_hist[l]);
   for (uint32_t l = 0; l < 5; l++) if (!(b->lent && l == c->nlevels)) hipFree(b->d_base[l]);
@@ -367,6 +381,13 @@ static int create_init(shk_ctx *c, const shk_config *cfg) {
     c->part[l].may_narrow = l >= 1 && l + 2 == c->nlevels && !words8;
     c->lv[l].cb = 32 - 16 - c->lv[c->nlevels - 1].bits;
   }
+  // No counting pass above the last level either (roll_stage): three levels, the middle one may be narrow, the last one may
+  // slot, and a bucket of the middle level's output gets so many keys of a full batch that six sigma of a clumpy share,
+  // 6 sqrt(8 m), are at most a tenth of it (m >= 28,800): below that the slots spread a bucket over too much empty range.
+  // SHK_ROLL_SLOTS=0: every batch takes the histogram pass
+  c->roll_slots = c->nlevels == 3 && c->part[1].may_narrow && c->part[2].may_slot &&
+                  !(getenv("SHK_ROLL_SLOTS") && atoi(getenv("SHK_ROLL_SLOTS")) == 0) &&
+                  cfg->max_batch_keys / (level_out(c, 1)) >= 28800;
   c->rounds_left = cfg->num_denoise;
   c->max_reads = cfg->max_batch_reads ? cfg->max_batch_reads : cfg->max_batch_bytes / 16 + 1024;
   { int rc = bufs_alloc(c, c, false); if (rc) return rc; }
@@ -621,36 +642,82 @@ static void launch_roll_scatter(const shk_ctx *c, ShkStageBufs *b, const ShkRoll
 // (the roll kernels take q_lo as a multiple of 256: q_lo = nslots * shard_index with nslots a power of two, so any other
 // q_lo needs nslots < 256, which is one region and one level)
 static bool roll_path(const shk_ctx *c) { return c->nlevels >= 2; }
-static int roll_stage(const shk_ctx *c, ShkStageBufs *b, const void *text, int on_device, uint64_t text_bytes, const uint64_t *chunk_off,
-                      const uint64_t *chunk_len, uint32_t nchunks, uint32_t chunk_first, uint32_t chunk_mul) {
-  if (!chunk_labels_ok(nchunks, chunk_first, chunk_mul)) return SHK_ERR_BATCH;
-  const uint8_t *dtext;
-  uint64_t nreads;
-  { int rc = parse_stage(c, b, text, on_device, text_bytes, chunk_off, chunk_len, nchunks, &dtext, &nreads); if (rc) return rc; }
+
+// Capacity of a slot above the last level for a mean share of m keys: the mean plus six sigma of a clumpy hash
+// distribution (a true k-mer comes ~8 times per batch, as slot_capacity() has it), rounded up to a multiple of `unit`.
+// Tight, not buffer-sized: whatever a slot does not use is address range the next level's streams have to cross.
+static uint64_t up_slot_capacity(double m, uint64_t unit) {
+  const uint64_t cp = (uint64_t)ceil(m + 6.0 * sqrt(8.0 * m + 1.0) + 16.0);
+  return (cp + unit - 1) / unit * unit;
+}
+
+// The parsed batch as the roll kernels take it: what roll_keys needs to run a second time (front_end, after an overflow)
+struct ShkRollBatch {
+  const uint8_t *dtext; uint64_t text_bytes, nreads;
+  uint32_t nchunks, chunk_first, chunk_mul;
+};
+
+// The roll kernels over a parsed batch, from the 2-bit staging on. slots: no histogram pass; digit d owns the slot
+// [d * roll_cap, (d + 1) * roll_cap) of d_words[0], d_base[1] holds the slots' bases, d_end[1] the buckets' ends and
+// d_scalars[DS_EXTENT] the positions of all slots; an overflow raises SHK_E_SLOT_FULL_UP (the caller's read-back).
+static int roll_keys(const shk_ctx *c, ShkStageBufs *b, const ShkRollBatch &R, bool slots) {
   const uint64_t P = 1ULL << c->lv[0].bits;
   // the first two levels' digits together, when they fit the histogram pass's LDS bins
   const uint32_t cb = c->lv[0].bits + c->lv[1].bits;
   const bool two = c->roll_two;
-  if (two) HIPCHK(hipMemsetAsync(b->d_hist[1], 0, (1ULL << cb) * 8, b->stream));
+  b->roll_cap = 0;
+  if (slots) {
+    // the host's only bound on the keys before they are hashed: a base needs a quality byte
+    const uint64_t U = c->cfg.max_batch_keys < R.text_bytes / 2 ? c->cfg.max_batch_keys : R.text_bytes / 2;
+    const uint64_t cap0 = up_slot_capacity((double)U / (double)P, 16);
+    if (P * cap0 <= words_cap(c)) b->roll_cap = cap0;
+  }
+  const uint64_t cap0 = b->roll_cap;
+  if (cap0) {
+    ProfScope ps(c, b, KP_RP_PREP);
+    hipLaunchKernelGGL(k_rp_slot_bases, dim3((uint32_t)(P / 256 + 1)), dim3(256), 0, b->stream, b->d_base[1], b->d_cursor, P, cap0, b->d_scalars + DS_EXTENT);
+  } else if (two) HIPCHK(hipMemsetAsync(b->d_hist[1], 0, (1ULL << cb) * 8, b->stream));
   else HIPCHK(hipMemsetAsync(b->d_hist[0], 0, P * 8, b->stream));
   ShkRollArgs A;
-  roll_args(c, b, A, dtext, text_bytes, chunk_first, chunk_mul);
+  roll_args(c, b, A, R.dtext, R.text_bytes, R.chunk_first, R.chunk_mul);
   A.q_lo = c->q_lo;
   A.dig_shift = c->lv[0].shift; A.dig_bits = c->lv[0].bits;
   A.hist = two ? b->d_hist[1] : b->d_hist[0]; A.hist_shift = two ? c->lv[1].shift : c->lv[0].shift; A.hist_bits = two ? cb : c->lv[0].bits;
   A.cursor = b->d_cursor; A.out = b->d_words[0];
-  { int rc = pack_stage(c, b, A, nreads, text_bytes, b->d_words[1]); if (rc) return rc; }     // (d_words[1]: the partition's other buffer, idle until its second level)
+  if (cap0) A.cap = P * cap0;
+  { int rc = pack_stage(c, b, A, R.nreads, R.text_bytes, b->d_words[1]); if (rc) return rc; }     // (d_words[1]: the partition's other buffer, idle until its second level)
+  if (cap0) {
+    launch_roll_scatter(c, b, A, R.nreads);
+    ProfScope ps(c, b, KP_RP_PREP);
+    hipLaunchKernelGGL(k_roll_slot_ends, dim3(1), dim3(c->threads < 256 ? c->threads : 256), 0, b->stream, (const uint64_t *)b->d_cursor, (uint32_t)P, cap0,
+                       b->d_end[1], b->d_scalars + DS_NWORDS, b->d_err);
+    HIPCHK(hipGetLastError());
+    return SHK_OK;
+  }
   { ProfScope ps(c, b, KP_ROLL_HIST);
-    launch_roll_hist(c, b, A, nreads, two);
+    launch_roll_hist(c, b, A, R.nreads, two);
     if (two) hipLaunchKernelGGL(k_roll_fold, dim3((uint32_t)(P / 256 + 1)), dim3(256), 0, b->stream, (const uint64_t *)b->d_hist[1], (uint32_t)P,
                                 1u << c->lv[1].bits, b->d_hist[0]); }
   // bucket bases = exclusive scan of the digit counts; its total is the number of key words
   if (run_scan<uint64_t>(c, b, b->d_hist[0], P, nullptr, b->d_base[1])) return SHK_ERR_HIP;
   HIPCHK(hipMemcpyAsync(b->d_scalars + DS_NWORDS, b->d_base[1] + P, 8, hipMemcpyDeviceToDevice, b->stream));
   HIPCHK(hipMemcpyAsync(b->d_cursor, b->d_base[1], P * 8, hipMemcpyDeviceToDevice, b->stream));
-  launch_roll_scatter(c, b, A, nreads);
+  launch_roll_scatter(c, b, A, R.nreads);
   HIPCHK(hipGetLastError());
   return SHK_OK;
+}
+
+// Does this batch run without counting passes above the last level? The plan allows it, the batch is narrow (the middle
+// level's slots hold narrow records) and two overflows in a row have not switched the upper slots off.
+static bool roll_slots_batch(const shk_ctx *c, const ShkStageBufs *b, uint32_t nchunks) {
+  return c->roll_slots && !b->up_off && nchunks <= (1u << c->lv[1].cb);
+}
+static int roll_stage(const shk_ctx *c, ShkStageBufs *b, const void *text, int on_device, uint64_t text_bytes, const uint64_t *chunk_off,
+                      const uint64_t *chunk_len, uint32_t nchunks, uint32_t chunk_first, uint32_t chunk_mul, ShkRollBatch *R) {
+  if (!chunk_labels_ok(nchunks, chunk_first, chunk_mul)) return SHK_ERR_BATCH;
+  R->text_bytes = text_bytes; R->nchunks = nchunks; R->chunk_first = chunk_first; R->chunk_mul = chunk_mul;
+  { int rc = parse_stage(c, b, text, on_device, text_bytes, chunk_off, chunk_len, nchunks, &R->dtext, &R->nreads); if (rc) return rc; }
+  return roll_keys(c, b, *R, roll_slots_batch(c, b, nchunks));
 }
 
 // What partition_stage reads (the number of words is in d_scalars[DS_NWORDS] as well), and its three producers
@@ -660,15 +727,21 @@ struct ShkPartInput {
   uint32_t first_level;  // 1: src[0] is partitioned by the first digit already and d_base[1] holds the bucket bases
   bool counted[2];       // counted[l]: the producer has filled d_hist[l]
   uint32_t nchunks;      // the words' chunk fields are chunk tags below this; 0: not known (or the field is a multiplicity)
+  uint64_t slot_cap0;    // first_level = 1 only, 0 = off: src[0] lies in slots of this many words per first digit, d_end[1] holds the
+                         // buckets' ends (ShkStageBufs::roll_cap); the middle level is then slotted too
+  bool redo;             // the batch's second time through the partition, after SHK_E_SLOT_FULL_UP: the last level's cursor set-up is
+                         // timed with the other preparations, so that k_rp_slot_cursors stays one launch per batch that tried slots
 };
 // roll_stage: d_words[0] sorted by the first digit; the second level is counted when the two levels' digits fit one pass
-static ShkPartInput part_from_roll(const shk_ctx *c, const ShkStageBufs *b, uint64_t n, uint32_t nchunks) { return {{b->d_words[0], nullptr}, {n, 0}, 1, 0, 1, {false, c->roll_two}, nchunks}; }
+static ShkPartInput part_from_roll(const shk_ctx *c, const ShkStageBufs *b, uint64_t n, uint32_t nchunks) {
+  return {{b->d_words[0], nullptr}, {n, 0}, 1, 0, 1, {false, c->roll_two && !b->roll_cap}, nchunks, b->roll_cap, false};
+}
 // hash_stage with hist0: d_words[0] in emission order, the first level counted
-static ShkPartInput part_from_hash(const ShkStageBufs *b, uint64_t n, uint32_t nchunks) { return {{b->d_words[0], nullptr}, {n, 0}, 1, 0, 0, {true, false}, nchunks}; }
+static ShkPartInput part_from_hash(const ShkStageBufs *b, uint64_t n, uint32_t nchunks) { return {{b->d_words[0], nullptr}, {n, 0}, 1, 0, 0, {true, false}, nchunks, 0, false}; }
 // the caller's words, read in place (no staging copy), in one of the context's own buffers or not. w2: a second source
 // (shk_stage_words_pair: both are counted into one histogram and scattered with one set of cursors)
 static ShkPartInput part_from_words(const ShkStageBufs *b, const uint64_t *w, uint64_t n, const uint64_t *w2 = nullptr, uint64_t n2 = 0) {
-  return {{w, w2}, {n, n2}, w2 ? 2 : 1, w == b->d_words[0] ? 0 : w == b->d_words[1] ? 1 : -1, 0, {false, false}, 0};
+  return {{w, w2}, {n, n2}, w2 ? 2 : 1, w == b->d_words[0] ? 0 : w == b->d_words[1] ? 1 : -1, 0, {false, false}, 0, 0, false};
 }
 
 // Last level: fixed-capacity region slots instead of a histogram pass over the keys + scan, when the output buffer
@@ -683,43 +756,68 @@ static uint32_t slot_capacity(const shk_ctx *c, uint64_t nregions, uint64_t nwor
   return cp >= 64 && (double)cp >= mean + 6.0 * sqrt(8.0 * mean + 1.0) + 16.0 ? (uint32_t)cp : 0;
 }
 
+// partition_stage's answer when a slotted level above the last one overflowed: nothing of the batch is committed, the
+// caller runs its front end again from the 2-bit staging on, with counted bases (front_end). Never leaves the library.
+#define SHK_RC_REDO_UP 0x5348
+
 // the words of `in` -> sorted by region in d_words[*dst]; region offsets in d_base[nlevels] (ShkStageBufs::region_cap)
 static int partition_stage(const shk_ctx *c, ShkStageBufs *b, const ShkPartInput &in, int *dst) {
   const uint64_t *n_p = b->d_scalars + DS_NWORDS;
   const uint64_t nmax = in.n[0] + in.n[1];
   { ProfScope ps(c, b, KP_RP_PREP);
     hipLaunchKernelGGL(k_rp_base1, dim3(1), dim3(64), 0, b->stream, n_p, b->d_base[0]); }
-  const uint32_t nwin = (uint32_t)(nmax / SHK_RP_TILE + 1);
   int cur = in.in_buf < 0 ? 1 : in.in_buf;   // the buffer the level's input occupies (neither: write to d_words[0] first)
   bool counted[4] = {in.counted[0], in.counted[1], false, false};
   bool narrow = false;   // the level in hand writes narrow records
+  bool up_checked = false;   // the error word has been read back behind the slotted upper levels
+  // Slotted levels above the last one (in.slot_cap0: a three-level context, so the level in hand is the middle one or the
+  // last). A slotted input has an extent in positions, which the window grids and the kernels' bounds take, next to its
+  // number of words, which the statistics and the merge take; its buckets end where d_end[l] says.
+  uint64_t ext = in.slot_cap0 ? in.slot_cap0 << c->lv[0].bits : nmax;      // positions of the input of the level in hand
+  const uint64_t *ext_p = in.slot_cap0 ? b->d_scalars + DS_EXTENT : n_p, *ends = in.slot_cap0 ? b->d_end[1] : nullptr;
   b->region_cap = 0;
   for (uint32_t l = in.first_level; l < c->nlevels; l++) {
     const ShkPartLevel &pl = c->part[l];
     const uint64_t nb = c->lv[l].nbuckets, P = 1ULL << c->lv[l].bits;
+    const bool last = l + 1 == c->nlevels;
     // 4-byte records between this level and the next: the plan allows it and every chunk tag of the call fits
     const bool narrow_in = narrow;
     narrow = pl.may_narrow && in.nchunks && in.nchunks <= (1u << c->lv[l].cb);
-    // the sources of this level: (words, their number on the device, their bucket bases, their number on the host)
-    struct Src { const uint64_t *w, *n_p, *base; uint64_t n; } srcs[2] = {{l == in.first_level ? in.src[0] : b->d_words[cur], n_p, b->d_base[l], nmax}, {}};
+    // the sources of this level: (words, their extent on the device, their bucket bases and ends, their extent on the host)
+    struct Src { const uint64_t *w, *n_p, *base, *end; uint64_t n; } srcs[2] = {{l == in.first_level ? in.src[0] : b->d_words[cur], ext_p, b->d_base[l], ends, ext}, {}};
     int nsrc = 1;
     if (l == 0 && in.nsrc == 2) {
-      srcs[0] = {in.src[0], b->d_scalars + DS_PAIR_LEN, b->d_scalars + DS_PAIR_BASE, in.n[0]};
-      srcs[1] = {in.src[1], b->d_scalars + DS_PAIR_LEN + 1, b->d_scalars + DS_PAIR_BASE + 2, in.n[1]};
+      srcs[0] = {in.src[0], b->d_scalars + DS_PAIR_LEN, b->d_scalars + DS_PAIR_BASE, nullptr, in.n[0]};
+      srcs[1] = {in.src[1], b->d_scalars + DS_PAIR_LEN + 1, b->d_scalars + DS_PAIR_BASE + 2, nullptr, in.n[1]};
       nsrc = 2;
     }
+    const uint32_t nwin = (uint32_t)(ext / SHK_RP_TILE + 1);
     // (a level that is counted already gains nothing from slots)
     uint32_t cap = pl.may_slot && !b->slots_off && !counted[l] ? slot_capacity(c, nb * P, nmax) : 0;
+    // the middle level behind slotted roll kernels: slots of narrow records for the batch's mean share, as many as its
+    // buffer holds (two records per word) at the most
+    uint64_t cap_up = 0;
+    if (in.slot_cap0 && !last) {
+      cap_up = up_slot_capacity((double)nmax / (double)(nb * P), 32);
+      const uint64_t room = 2 * words_cap(c) / (nb * P) / 32 * 32;
+      if (cap_up > room) cap_up = room;
+    }
     { ProfScope ps(c, b, KP_RP_PREP);
-      hipLaunchKernelGGL(k_rp_tile_first, dim3(nwin / 256 + 1), dim3(256), 0, b->stream, b->d_base[l], (uint32_t)nb, n_p, b->d_tfb); }
+      hipLaunchKernelGGL(k_rp_tile_first, dim3(nwin / 256 + 1), dim3(256), 0, b->stream, b->d_base[l], (uint32_t)nb, ext_p, b->d_tfb); }
     for (;;) {
       ShkRpLevel lvl = c->lv[l];
 #ifdef SHK_DIAGNOSTICS   // timing ablations give INVALID results: compiled into diagnostic builds only (make DIAG=1)
       if (const char *e = getenv("SHK_RP_ABLATE")) lvl.ablate = (uint32_t)atoi(e);
 #endif
       uint64_t *cursor = b->d_cursor;
-      if (cap) {
-        ProfScope ps(c, b, KP_RP_SLOTS);
+      if (cap_up) {
+        ProfScope ps(c, b, KP_RP_PREP);
+        cursor = b->d_end[l + 1];            // (ends up as the buckets' ends)
+        lvl.slot_cap = (uint32_t)cap_up;
+        hipLaunchKernelGGL(k_rp_slot_bases, dim3((uint32_t)((nb * P) / 256 + 1 < 4096 ? (nb * P) / 256 + 1 : 4096)), dim3(256), 0, b->stream, b->d_base[l + 1],
+                           cursor, nb * P, cap_up, b->d_scalars + DS_EXTENT + 1);
+      } else if (cap) {
+        ProfScope ps(c, b, in.redo ? KP_RP_PREP : KP_RP_SLOTS);
         cursor = b->d_base[l + 1];           // (ends up as the regions' end positions)
         lvl.slot_cap = cap;
         hipLaunchKernelGGL(k_rp_slot_cursors, dim3((uint32_t)((nb * P) / 256 + 1 < 4096 ? (nb * P) / 256 + 1 : 4096)), dim3(256), 0, b->stream, cursor, nb * P, cap);
@@ -740,11 +838,11 @@ static int partition_stage(const shk_ctx *c, ShkStageBufs *b, const ShkPartInput
           const uint32_t wt = nwin / 4096 + 1;   // windows per workgroup
           for (int si = 0; si < nsrc; si++)
             if (narrow_in)
-              hipLaunchKernelGGL(k_rp_hist<true>, dim3(nwin / wt + 1), dim3(c->threads), 0, b->stream, srcs[si].w, srcs[si].n_p, srcs[si].base, b->d_tfb,
-                                 c->lv[l], b->d_hist[l], wt);
+              hipLaunchKernelGGL(k_rp_hist<true>, dim3(nwin / wt + 1), dim3(c->threads), 0, b->stream, srcs[si].w, srcs[si].n_p, srcs[si].base, srcs[si].end,
+                                 b->d_tfb, c->lv[l], b->d_hist[l], wt);
             else
-              hipLaunchKernelGGL(k_rp_hist<false>, dim3(nwin / wt + 1), dim3(c->threads), 0, b->stream, srcs[si].w, srcs[si].n_p, srcs[si].base, b->d_tfb,
-                                 c->lv[l], b->d_hist[l], wt);
+              hipLaunchKernelGGL(k_rp_hist<false>, dim3(nwin / wt + 1), dim3(c->threads), 0, b->stream, srcs[si].w, srcs[si].n_p, srcs[si].base, srcs[si].end,
+                                 b->d_tfb, c->lv[l], b->d_hist[l], wt);
         }
         // bases
         if (c->lv[l].ng_log2) {
@@ -766,32 +864,39 @@ static int partition_stage(const shk_ctx *c, ShkStageBufs *b, const ShkPartInput
           const dim3 wide((uint32_t)(S.n >> SHK_RP_TILE0_LOG2) + 1);
           if (narrow && pl.scatter == RP_SCATTER_WIDE)
             hipLaunchKernelGGL((k_rp_scatter<SHK_RP_TILE0_LOG2, 1024, 256, RP_NARROW_OUT>), wide, dim3(1024), 0, b->stream, S.w, b->d_words[cur ^ 1], S.n_p,
-                               S.base, b->d_tfb, lvl, cursor, b->d_err);
+                               S.base, S.end, b->d_tfb, lvl, cursor, b->d_err);
           else if (narrow)
             hipLaunchKernelGGL((k_rp_scatter<12, SHK_RP_THREADS, SHK_RP_MAXP, RP_NARROW_OUT>), dim3((uint32_t)(S.n / SHK_RP_TILE + 1)), dim3(SHK_RP_THREADS), 0,
-                               b->stream, S.w, b->d_words[cur ^ 1], S.n_p, S.base, b->d_tfb, lvl, cursor, b->d_err);
+                               b->stream, S.w, b->d_words[cur ^ 1], S.n_p, S.base, S.end, b->d_tfb, lvl, cursor, b->d_err);
           else if (narrow_in)
             hipLaunchKernelGGL((k_rp_scatter<12, SHK_RP_THREADS, SHK_RP_MAXP, RP_NARROW_IN>), dim3((uint32_t)(S.n / SHK_RP_TILE + 1)), dim3(SHK_RP_THREADS), 0,
-                               b->stream, S.w, b->d_words[cur ^ 1], S.n_p, S.base, b->d_tfb, lvl, cursor, b->d_err);
+                               b->stream, S.w, b->d_words[cur ^ 1], S.n_p, S.base, S.end, b->d_tfb, lvl, cursor, b->d_err);
           else if (pl.scatter == RP_SCATTER_GROUPED)      // (window groups are defined on the first level's 16384-key windows: SHK_RP_TILE0_LOG2)
-            hipLaunchKernelGGL((k_rp_scatter<SHK_RP_TILE0_LOG2, 1024>), wide, dim3(1024), 0, b->stream, S.w, b->d_words[cur ^ 1], S.n_p, S.base,
+            hipLaunchKernelGGL((k_rp_scatter<SHK_RP_TILE0_LOG2, 1024>), wide, dim3(1024), 0, b->stream, S.w, b->d_words[cur ^ 1], S.n_p, S.base, S.end,
                                b->d_tfb, lvl, cursor, b->d_err);
           else if (pl.scatter == RP_SCATTER_WIDE)
-            hipLaunchKernelGGL((k_rp_scatter<SHK_RP_TILE0_LOG2, 1024, 256>), wide, dim3(1024), 0, b->stream, S.w, b->d_words[cur ^ 1], S.n_p, S.base,
+            hipLaunchKernelGGL((k_rp_scatter<SHK_RP_TILE0_LOG2, 1024, 256>), wide, dim3(1024), 0, b->stream, S.w, b->d_words[cur ^ 1], S.n_p, S.base, S.end,
                                b->d_tfb, lvl, cursor, b->d_err);
           else
             hipLaunchKernelGGL((k_rp_scatter<12, SHK_RP_THREADS>), dim3((uint32_t)(S.n / SHK_RP_TILE + 1)), dim3(SHK_RP_THREADS), 0, b->stream, S.w,
-                               b->d_words[cur ^ 1], S.n_p, S.base, b->d_tfb, lvl, cursor, b->d_err);
+                               b->d_words[cur ^ 1], S.n_p, S.base, S.end, b->d_tfb, lvl, cursor, b->d_err);
         } }
-      if (!cap) break;
-      // slots: did every region fit?
+      // No read-back behind a level without slots, nor behind the slotted middle level (the last level's shows its bit) --
+      // unless the last level behind slotted upper ones has no slots of its own this time: then theirs is fetched here
+      if (!cap && !(in.slot_cap0 && last && !up_checked)) break;
       uint32_t bits = 0;
       if (fetch_err(b, &bits)) return SHK_ERR_HIP;
+      if (bits & SHK_E_SLOT_FULL_UP) return SHK_RC_REDO_UP;
       if (bits & ~SHK_E_SLOT_FULL) return map_err_bits(bits & ~SHK_E_SLOT_FULL);
+      if (in.slot_cap0 && !up_checked) { b->up_overflows = 0; up_checked = true; }
+      if (!cap) break;
+      // slots: did every region fit?
       if (!bits) { b->region_cap = cap; b->slot_overflows = 0; break; }
       if (++b->slot_overflows >= 2) b->slots_off = 1;
       cap = 0;                               // a region overflowed its slot: the same level again with exact bases
     }
+    if (cap_up) { ext = (nb * P) * cap_up; ext_p = b->d_scalars + DS_EXTENT + 1; ends = b->d_end[l + 1]; }
+    else { ext = nmax; ext_p = n_p; ends = nullptr; }
     cur ^= 1;
   }
   HIPCHK(hipGetLastError());
@@ -1456,17 +1561,33 @@ static int finish(shk_ctx *c, int rc) {
 static int front_end(const shk_ctx *c, ShkStageBufs *b, const void *text, int on_device, uint64_t text_bytes, const uint64_t *chunk_off,
                      const uint64_t *chunk_len, uint32_t nchunks, uint64_t *nwords, int *dst, uint32_t *region_cap) {
   const bool roll = roll_path(c);
+  ShkRollBatch R = {};
+  bool part_redo = false;
   // (one-level contexts: the hash kernel, which counts the level's digits as it goes)
-  int rc = roll ? roll_stage(c, b, text, on_device, text_bytes, chunk_off, chunk_len, nchunks, 0, 1)
+  int rc = roll ? roll_stage(c, b, text, on_device, text_bytes, chunk_off, chunk_len, nchunks, 0, 1, &R)
                 : hash_stage(c, b, text, on_device, text_bytes, chunk_off, chunk_len, nchunks, 0, 1, true);
-  if (rc) return rc;
-  uint32_t bits = 0;
-  HIPCHK(hipMemcpyAsync(b->h_pinned + HP_NWORDS, b->d_scalars + DS_NWORDS, 8, hipMemcpyDeviceToHost, b->stream));
-  if (fetch_err(b, &bits)) return SHK_ERR_HIP;
-  if (bits) return map_err_bits(bits);
-  *nwords = b->h_pinned[HP_NWORDS];
-  if (*nwords > c->cfg.max_batch_keys) return SHK_ERR_BATCH;
-  rc = partition_stage(c, b, roll ? part_from_roll(c, b, *nwords, nchunks) : part_from_hash(b, *nwords, nchunks), dst);
+  for (;;) {
+    if (rc) return rc;
+    uint32_t bits = 0;
+    HIPCHK(hipMemcpyAsync(b->h_pinned + HP_NWORDS, b->d_scalars + DS_NWORDS, 8, hipMemcpyDeviceToHost, b->stream));
+    if (fetch_err(b, &bits)) return SHK_ERR_HIP;
+    if (!(bits & SHK_E_SLOT_FULL_UP)) {
+      if (bits) return map_err_bits(bits);
+      *nwords = b->h_pinned[HP_NWORDS];
+      if (*nwords > c->cfg.max_batch_keys) return SHK_ERR_BATCH;
+      ShkPartInput in = roll ? part_from_roll(c, b, *nwords, nchunks) : part_from_hash(b, *nwords, nchunks);
+      in.redo = part_redo;
+      rc = partition_stage(c, b, in, dst);
+      if (rc != SHK_RC_REDO_UP) break;
+      part_redo = true;
+    }
+    // A slotted level above the last one overflowed (the roll kernels' level: seen in the read-back above; the middle one:
+    // in the read-back behind the last level). Nothing is committed, the parse results are intact, the pack buffer is
+    // not (the middle level wrote over it): the batch again from the 2-bit staging on, with counted bases. Two such
+    // batches in a row switch the upper slots off for this front end.
+    if (++b->up_overflows >= 2) b->up_off = 1;
+    rc = roll_keys(c, b, R, false);
+  }
   *region_cap = b->region_cap;
   return rc;
 }
@@ -1525,9 +1646,9 @@ static int front_init(shk_ctx *c) {
   // the roll kernels write d_words[0]; every further level flips: the last one lands in d_words[(nlevels - 1) & 1]
   F->par = roll_path(c) ? (int)((c->nlevels - 1) & 1) : (int)(c->nlevels & 1);
   const uint64_t capk = c->cfg.max_batch_keys;
-  if (dmalloc(&F->scratch, capk + 1)) return SHK_ERR_HIP;
+  if (dmalloc(&F->scratch, words_cap(c) + 1)) return SHK_ERR_HIP;
   for (int k2 = 0; k2 < 2; k2++)
-    if (dmalloc(&F->slot[k2].words, capk + 1) || dmalloc(&F->slot[k2].base, level_out(c, c->nlevels - 1) + 2)) return SHK_ERR_HIP;
+    if (dmalloc(&F->slot[k2].words, words_cap(c) + 1) || dmalloc(&F->slot[k2].base, level_out(c, c->nlevels - 1) + 2)) return SHK_ERR_HIP;
   return SHK_OK;
 }
 static void front_destroy(shk_ctx *c) {
@@ -1753,12 +1874,12 @@ extern "C" int shk_route_words(shk_ctx *c, uint64_t nwords, uint32_t nshards, ui
   int rc = owner_bins(c, nshards, 1, [&] {
     ProfScope ps(c, KP_RP_HIST);
     const uint32_t wt = nwin / 4096 + 1;
-    hipLaunchKernelGGL(k_rp_hist<false>, dim3(nwin / wt + 1), dim3(c->threads), 0, c->stream, c->d_words[0], n_p, c->d_base[0], c->d_tfb, lv, c->d_block_sums + ROUTE_HIST, wt);
+    hipLaunchKernelGGL(k_rp_hist<false>, dim3(nwin / wt + 1), dim3(c->threads), 0, c->stream, c->d_words[0], n_p, c->d_base[0], (const uint64_t *)nullptr, c->d_tfb, lv, c->d_block_sums + ROUTE_HIST, wt);
   }, counts, base);
   if (rc) return finish(c, rc);
   { ProfScope ps(c, KP_RP_SCATTER);
     hipLaunchKernelGGL((k_rp_scatter<12, SHK_RP_THREADS>), dim3(nwin), dim3(SHK_RP_THREADS), 0, c->stream, c->d_words[0], send, n_p,
-                       c->d_base[0], c->d_tfb, lv, c->d_block_sums + ROUTE_CURSOR, c->d_err); }
+                       c->d_base[0], (const uint64_t *)nullptr, c->d_tfb, lv, c->d_block_sums + ROUTE_CURSOR, c->d_err); }
   HIPCHK(hipGetLastError());
   *d_out = send;
   return finish(c, 0);

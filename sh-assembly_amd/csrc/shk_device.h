@@ -37,7 +37,9 @@
 #define SHK_E_BAD_FASTQ    (1u << 5)   // read longer than 65535 / k out of range
 #define SHK_E_KEYS_FULL    (1u << 6)   // batch produced more keys than the key buffer holds
 #define SHK_E_RUN_TOO_LONG (1u << 7)
-                                       // (bit 8 is free: the flags keep their numbers, shk/__init__.py hard-codes some)
+#define SHK_E_SLOT_FULL_UP (1u << 8)   // a slotted level ABOVE the last one (k_roll_scatter, the middle k_rp_scatter): a bucket got more words than its
+                                       // slot holds (host runs the batch's front end again with counted bases). Apart from SHK_E_SLOT_FULL, whose redo
+                                       // is the last level alone. (The flags keep their numbers: shk/__init__.py hard-codes some)
 #define SHK_E_FUSED        (1u << 9)   // the one-pass deNoise point met a region it does not handle (host takes the three-pass path)
 #define SHK_E_SLOT_FULL    (1u << 10)  // last partition level with fixed-capacity region slots: a region got more words (host redoes the level with exact bases)
 
