@@ -263,7 +263,10 @@ int shk_stage_point_walk(shk_ctx *ctx, int64_t carry, int64_t prev_fp, int last,
                          uint64_t state_out[2], uint64_t *nprot, uint32_t *err_bits);
 int shk_stage_point_finish(shk_ctx *ctx, shk_point *out, shk_summary *accept);
 
-/* One deNoise round now (the reference's --endDeNoise round; does not use up num_denoise). */
+/* One deNoise round now (the reference's --endDeNoise round; does not use up num_denoise).
+ * Like every round (those fired inside the counting calls, shk_stage_try_denoise, the shk_stage_point_* steps) it drops
+ * what qf_remove_singletons drops, whatever traveled marks the table carries (see shk_lookup): the reference's sweep
+ * never looks at them, and neither does this one. */
 int shk_denoise(shk_ctx *ctx, uint64_t *removed);
 
 /* ---- filter-to-filter utilities
@@ -341,7 +344,19 @@ int shk_import_cqf(shk_ctx *ctx, const char *path);
 int shk_import_blocks(shk_ctx *ctx, const void *host_src, uint64_t nbytes, uint64_t nelts, uint64_t ndistinct);
 
 /* mode 0: count + is_traveled, 1: count + set_traveled (returns the bit before), 2: count only.
- * keys/counts/was_traveled are host pointers unless on_device != 0. was_traveled may be NULL. */
+ * keys/counts/was_traveled are host pointers unless on_device != 0. was_traveled may be NULL. A key outside this
+ * context's quotient range answers 0 and marks nothing. One call may hold a key several times: under mode 1 exactly one
+ * of them sees the bit unset (which one is not defined; the reference is sequential).
+ * Traveled marks -- the contract:
+ *   - they belong to readers: shk_lookup mode 1, shk_extend_forward / shk_unitigs_add_seeds with mark_traveled,
+ *     shk_unitigs_add_reads and shk_select_seeds(use_traveled) set them on the first slot of an entry, mode 0 and the
+ *     marking calls read them, shk_export_* / shk_import_* carry them;
+ *   - no mark influences what any writer computes: counts, statistics, what a deNoise round removes and the bytes written
+ *     are those of a table nobody marked;
+ *   - every call that rebuilds the table leaves all traveled words zero: the counting calls, shk_insert_counted,
+ *     shk_merge / shk_multi_merge / shk_import_shards, shk_denoise, shk_stage_commit / shk_stage_accept, shk_intersect.
+ *   The reference leaves stale bits at slot positions when an insert shifts slots (its bits do not move with the
+ *   entries); that is not reproduced. */
 int shk_lookup(shk_ctx *ctx, const uint64_t *keys, uint64_t n, int on_device, int mode,
                uint64_t *counts, uint8_t *was_traveled);
 

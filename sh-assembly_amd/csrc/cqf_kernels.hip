@@ -242,7 +242,8 @@ __device__ __forceinline__ void shk_store_image(const ShkMergeArgs &A, uint32_t 
 // OLDREC: the old runs come from the region's previous spill record (A.orec: 256 length bytes + the runs' bytes back to
 // back in quotient order) instead of its blocks of table A, which then need not exist (lazy placement, shk_api.hip). No
 // image, no rank/select: a lane's four length bytes say which of its quotients have a run, a wave sum of the lanes' byte
-// totals where its first run starts. Not for the write pass, nor for a deNoise round that reads traveled bits.
+// totals where its first run starts. Not for the write pass, nor for a deNoise round: that one reads the protection
+// marks k_denoise_marks has just put into table A's traveled words (its own marks only -- a reader's are zeroed first).
 template <int MODE, int IMGB, bool FUSED = false, bool OLDREC = false>
 __global__ void __launch_bounds__(SHK_MERGE_GROUP) k_region_merge(ShkMergeArgs A) {
   static_assert(!FUSED || MODE == 3, "the one-pass deNoise point is a spill-mode pass");
@@ -1219,8 +1220,20 @@ __device__ uint64_t shk_g_first_nonempty(const uint8_t *t, uint64_t from, uint64
 // (CQF_mt.h:888-895) and, inside a range, never visits a cluster that STARTS on the range's
 // last slot (`while(start < end_bucket_id)`, CQF_mt.h:1024, gqf.c:2881). Such a cluster is
 // a single count-1 slot; it survives the round. This kernel reproduces the walk on table A
-// and marks those slots by setting their traveled bit (zero otherwise during a build); the
-// merge kernels in denoise mode keep marked entries. One thread: the walk is a dependent chain.
+// and marks those slots by setting their traveled bit; the merge kernels in denoise mode keep
+// marked entries. The bits must be zero when it starts: a table a rebuild wrote has none, and
+// where a reader or an import may have left some the host launches k_clear_traveled first
+// (shk_api.hip: marks_launch). One thread: the walk is a dependent chain.
+// Traveled marks belong to readers and no writer may see them: zero the traveled word of every block (8 bytes at
+// offset 17 of an 89-byte block, so no wider store is aligned in every block). One thread per block.
+__global__ void k_clear_traveled(uint8_t *tab, uint64_t nblocks) {
+  const uint64_t b = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= nblocks) return;
+  uint8_t *p = tab + b * SHK_BLOCK_BYTES + SHK_OFF_TRAV;
+#pragma unroll
+  for (int j = 0; j < 8; j++) p[j] = 0;
+}
+
 __global__ void k_denoise_marks(uint8_t *tab, uint64_t nslots, uint64_t xnslots, uint64_t nblocks, uint64_t min_len,
                                 unsigned long long *nmarked) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
@@ -1397,7 +1410,7 @@ __device__ __forceinline__ uint64_t shk_lookup_one(uint8_t *tab, uint64_t key, u
   uint8_t trav = 0;
   if (q < nslots && ((shk_g_occ(tab, q >> 6) >> (q & 63)) & 1)) {
     uint64_t rs = q == 0 ? 0 : shk_g_run_end(tab, q - 1) + 1;
-    if (rs < q) rs = q;
+    if (rs < q) rs = q;     // (as gqf.c:2454 has it; never taken here: shk_g_run_end(x) >= x on both of its ways out)
     for (;;) {
       // decode_counter on the table in HBM
       const unsigned r0 = shk_g_slot(tab, rs);

@@ -173,6 +173,9 @@ struct shk_ctx : ShkStageBufs {
   int rec_live;                 // 1: spill[live] + fin[cur] describe the live table (a pass may take its old side from them)
   int table_stale;              // 1: tab[cur] has not been written from them yet, or its placement failed (implies rec_live)
   int lazy_ok;                  // 0: every commit places (SHK_LAZY_PLACE=0, or the second record buffer did not fit)
+  int foreign_marks;            // 1: tab[cur] may hold traveled bits a reader set (lookup mode 1, the marking Contiger calls) or
+                                // an import brought in; a deNoise round zeroes them before its own marks (marks_launch). A
+                                // rebuild that makes the other table live clears the flag: rebuilt tables have no marks
   uint32_t *d_over_list;
   // what the spill records currently describe (a write pass may use them only for the same request)
   int spill_valid; const uint64_t *spill_words; uint32_t spill_lo, spill_hi; int spill_denoise, spill_big;
@@ -405,6 +408,7 @@ static int create_init(shk_ctx *c, const shk_config *cfg) {
   if (const char *e = getenv("SHK_SAMPLE_STRIDE")) c->sample_stride = (uint32_t)atoi(e);
   else if (c->nregions < (1u << 14)) c->sample_stride = 0;
   c->lazy_ok = 1;
+  c->foreign_marks = 0;
   if (const char *e = getenv("SHK_LAZY_PLACE")) c->lazy_ok = atoi(e) != 0;
   if (dmalloc(&c->spill[0], (uint64_t)c->nregions * SHK_SPILL_STRIDE) || dmalloc(&c->d_over_list, (uint64_t)c->nregions + 1)) return SHK_ERR_HIP;
   { uint64_t nt = c->nregions / SHK_RSCAN_TILE + 2;
@@ -1003,7 +1007,8 @@ static int ensure_chist(shk_ctx *c) {
 // spill: the summary keeps the runs for k_region_place (a write pass for the same request only places them)
 static int merge_summary(shk_ctx *c, const uint64_t *words, uint32_t lo, uint32_t hi, int denoise, MergeOut *o,
                          bool with_chist, bool spill) {
-  // (a deNoise round reads the traveled bits k_denoise_marks left in the table: its callers have synced it)
+  // (a deNoise round reads the protection marks k_denoise_marks has just left in the table's traveled words -- and only
+  // those: marks_launch has synced the table and zeroed whatever a reader or an import had set before)
   const bool rec = c->rec_live && !denoise;
   if (!rec) { int rc = table_sync(c); if (rc) return rc; }
   ShkMergeArgs A;
@@ -1058,6 +1063,7 @@ static int merge_write(shk_ctx *c, const uint64_t *words, uint32_t lo, uint32_t 
     c->rec_live = 1; c->table_stale = 1;
     c->spill_valid = 0;
     c->cur ^= 1;
+    c->foreign_marks = 0;       // (the placement zeroes the table first)
     return SHK_OK;
   }
   if (!match || c->spill_nover) { int rc = table_sync(c); if (rc) return rc; }   // (the write pass reads table A)
@@ -1088,15 +1094,28 @@ static int merge_write(shk_ctx *c, const uint64_t *words, uint32_t lo, uint32_t 
   HIPCHK(hipGetLastError());
   c->rec_live = 0; c->table_stale = 0;
   c->cur ^= 1;
+  c->foreign_marks = 0;         // (table B was zeroed and its traveled words are never written)
+  return SHK_OK;
+}
+
+// The protection marks of a deNoise round on the live table (k_denoise_marks): the only traveled bits a writer ever reads.
+// Marks belong to readers and influence no writer (include/shk.h), so whatever a marking lookup, a marking Contiger call
+// or an import may have left in tab[cur] is zeroed first. A build that never marks launches nothing here but the walk.
+static int marks_launch(shk_ctx *c) {
+  const uint64_t ml = c->cfg.min_denoise_len ? c->cfg.min_denoise_len : (1ULL << 20);
+  { int rc = table_sync(c); if (rc) return rc; }
+  ProfScope ps(c, KP_MARKS);
+  if (c->foreign_marks) {
+    hipLaunchKernelGGL(k_clear_traveled, dim3((uint32_t)((c->nblocks + 255) / 256)), dim3(256), 0, c->stream, c->tab[c->cur], c->nblocks);
+    c->foreign_marks = 0;
+  }
+  hipLaunchKernelGGL(k_denoise_marks, dim3(1), dim3(64), 0, c->stream, c->tab[c->cur], c->nslots, c->xnslots, c->nblocks,
+                     ml, (unsigned long long *)(c->d_scalars + DS_MARKS));
   return SHK_OK;
 }
 
 static int denoise_round_once(shk_ctx *c, uint64_t *removed) {
-  uint64_t ml = c->cfg.min_denoise_len ? c->cfg.min_denoise_len : (1ULL << 20);
-  { int rc = table_sync(c); if (rc) return rc; }
-  { ProfScope ps(c, KP_MARKS);
-    hipLaunchKernelGGL(k_denoise_marks, dim3(1), dim3(64), 0, c->stream, c->tab[c->cur], c->nslots, c->xnslots, c->nblocks,
-                       ml, (unsigned long long *)(c->d_scalars + DS_MARKS)); }
+  { int rc = marks_launch(c); if (rc) return rc; }
   MergeOut o;
   int rc = merge_summary(c, nullptr, 0, 0, 1, &o, false, true);
   if (rc) return rc;
@@ -1114,11 +1133,7 @@ static int denoise_round_once(shk_ctx *c, uint64_t *removed) {
 // trigger would be reached again inside [lo, hi]: the caller then runs the plain round.
 static int denoise_with_rest(shk_ctx *c, const uint64_t *words, uint32_t lo, uint32_t hi, shk_batch_stats *st, bool *done) {
   *done = false;
-  uint64_t ml = c->cfg.min_denoise_len ? c->cfg.min_denoise_len : (1ULL << 20);
-  { int rc = table_sync(c); if (rc) return rc; }
-  { ProfScope ps(c, KP_MARKS);
-    hipLaunchKernelGGL(k_denoise_marks, dim3(1), dim3(64), 0, c->stream, c->tab[c->cur], c->nslots, c->xnslots, c->nblocks,
-                       ml, (unsigned long long *)(c->d_scalars + DS_MARKS)); }
+  { int rc = marks_launch(c); if (rc) return rc; }
   MergeOut o;
   int rc = merge_summary(c, words, lo, hi, 1, &o, false, true);
   if (rc) return rc;
@@ -2043,11 +2058,7 @@ extern "C" int shk_stage_accept(shk_ctx *c, const shk_summary *s) {
 extern "C" int shk_stage_try_denoise(shk_ctx *c, uint32_t lo, uint32_t hi, shk_summary *out) {
   if (!c || !out || hi < lo || hi >= SHK_MAX_CHUNKS) return SHK_ERR_ARG;
   HIPCHK(hipSetDevice(c->dev));
-  uint64_t ml = c->cfg.min_denoise_len ? c->cfg.min_denoise_len : (1ULL << 20);
-  { int rc = table_sync(c); if (rc) return rc; }
-  { ProfScope ps(c, KP_MARKS);
-    hipLaunchKernelGGL(k_denoise_marks, dim3(1), dim3(64), 0, c->stream, c->tab[c->cur], c->nslots, c->xnslots, c->nblocks,
-                       ml, (unsigned long long *)(c->d_scalars + DS_MARKS)); }
+  { int rc = marks_launch(c); if (rc) return rc; }
   MergeOut o;
   int rc = merge_summary(c, c->d_words[c->staged], lo, hi, 1, &o, false, true);
   prof_collect(c);
@@ -2225,6 +2236,7 @@ extern "C" int shk_import_blocks(shk_ctx *c, const void *src, uint64_t nbytes, u
   if (!c || !src || nbytes != c->table_bytes) return SHK_ERR_ARG;
   HIPCHK(hipSetDevice(c->dev));
   c->rec_live = 0; c->table_stale = 0; c->spill_valid = 0;   // (the table is the truth again)
+  c->foreign_marks = 1;         // (a .cqf written behind Contiger carries its traveled words; they are kept for the readers)
   HIPCHK(hipMemcpyAsync(c->tab[c->cur], src, nbytes, hipMemcpyHostToDevice, c->stream));
   { ProfScope ps(c, KP_MISC);
     hipLaunchKernelGGL(k_build_fin, dim3(c->nregions / 256 + 1), dim3(256), 0, c->stream, c->tab[c->cur], c->nslots,
@@ -2257,6 +2269,7 @@ extern "C" int shk_lookup(shk_ctx *c, const uint64_t *keys, uint64_t n, int on_d
   HIPCHK(hipSetDevice(c->dev));
   { int rc = table_sync(c); if (rc) return rc; }
   uint64_t *dk = nullptr, *dc = nullptr; uint8_t *dt = nullptr;
+  if (mode == 1) c->foreign_marks = 1;
   if (on_device) { dk = (uint64_t *)keys; dc = counts; dt = was_traveled; }
   else {
     HIPCHK(hipMalloc((void **)&dk, n * 8)); HIPCHK(hipMalloc((void **)&dc, n * 8)); HIPCHK(hipMalloc((void **)&dt, n));
@@ -2492,6 +2505,7 @@ static int rebuild2_run(shk_ctx *c, const uint8_t *tab1, const uint64_t *fin1, c
   HIPCHK(hipGetLastError());
   c->rec_live = 0; c->table_stale = 0;
   c->cur ^= 1;
+  c->foreign_marks = 0;
   *newd_out = newd; *added_out = added;
   return SHK_OK;
 }
@@ -2699,6 +2713,7 @@ extern "C" int shk_import_shards(shk_ctx *c, const void *const *shard_blocks, co
   for (auto p : own) hipFree(p);
   for (auto p : fins) hipFree(p);
   if (!rc) { c->nelts = nelts ? nelts : added; c->ndistinct = ndistinct ? ndistinct : newd; }
+  // (the shards' tables are laid out again by the merge, which writes no traveled word: nothing foreign comes in here)
   return finish(c, rc);
 }
 
@@ -2720,6 +2735,7 @@ extern "C" int shk_select_seeds(shk_ctx *c, const void *text, int text_on_device
   struct Scratch { char *s = nullptr; uint32_t *c = nullptr; ~Scratch() { hipFree(s); hipFree(c); } } w;
   if (dmalloc(&w.s, nreads * k) || dmalloc(&w.c, nreads)) return SHK_ERR_HIP;
   char *ds = w.s; uint32_t *dc = w.c;
+  if (use_traveled) c->foreign_marks = 1;
   { ProfScope ps(c, KP_WALK);
     hipLaunchKernelGGL(k_select_seeds, dim3((uint32_t)((nreads + 255) / 256)), dim3(256), 0, c->stream, c->tab[c->cur], c->q_lo, c->nslots,
                        c->cfg.hb, dtext, c->d_rd_start, c->d_rd_end, (uint64_t)0, nreads, k, count_min, count_max, use_traveled ? 1 : 2, ds, dc); }
@@ -2773,6 +2789,7 @@ extern "C" int shk_extend_forward(shk_ctx *c, const char *cur_kmers, const char 
     return SHK_ERR_HIP;
   HIPCHK(hipMemcpyAsync(w.dk, cur_kmers, nk, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(w.df, first_kmers, nk, hipMemcpyHostToDevice, c->stream));
+  if (mark_traveled) c->foreign_marks = 1;
   { ProfScope ps(c, KP_WALK);
     char *dk = w.dk, *df = w.df, *db = w.db;          // (plain pointers: the launch must not capture the owning struct)
     uint32_t *dc = w.dc, *dn = w.dn, *dnc = w.dnc;
@@ -2985,6 +3002,7 @@ static int ug_bind(shk_unitig_set *u, shk_ctx *c, uint32_t k, uint64_t amin, uin
 static int ug_run(shk_unitig_set *u, uint32_t nactive, int mark) {
   shk_ctx *c = u->c;
   { int rc = table_sync(c); if (rc) return rc; }
+  if (mark) c->foreign_marks = 1;
   // Extensions per contig and launch. A launch lasts as long as its longest walk while the neighbours that the short
   // ones queued wait for the next one: with many contigs open, short launches keep the frontier moving (2 M unitigs of a
   // 100x C. elegans graph, 126 M extensions: 1.25 s at 2048 steps per launch, 0.92 at 512, 0.56 at 128, 0.49 at 64, 0.47 at
@@ -3073,6 +3091,7 @@ extern "C" int shk_unitigs_add_reads(shk_ctx *c, shk_unitig_set *u, const void *
   // (:1871-1873). Selecting all seeds of a batch at once would walk every unitig once per read that covers it, so the
   // reads are taken in slices that grow geometrically: the walks of one slice mark their unitigs before the next, four
   // times larger, slice looks at its reads -- the duplicates stay a small multiple of the number of unitigs.
+  c->foreign_marks = 1;
   uint64_t total_seeds = 0, lo = 0, slice = 16384;
   if (const char *e = getenv("SHK_SEED_SLICE")) { long long v = atoll(e); if (v > 0) slice = (uint64_t)v; }
   while (lo < nreads) {
