@@ -78,6 +78,12 @@ typedef struct shk_config {
   uint64_t max_batch_bytes;        /* capacity: FASTQ text bytes per shk_count_chunks call */
   uint64_t max_batch_keys;         /* capacity: k-mers per batch */
   uint64_t max_batch_reads;        /* capacity: reads per batch (0 = max_batch_bytes/16) */
+                                   /* Besides the text, read and key buffers these three size, a context keeps the newline
+                                    * flags of the text in hand, one bit per text byte: max(max_batch_bytes, 4 * max_batch_keys) / 8
+                                    * bytes (+ 16), once more in a context that has used shk_prepare_chunks. Device text of more
+                                    * than four bytes per key makes a call grow them to text_bytes / 8 (never back); if that
+                                    * allocation fails the call reads the text a second time instead. SHK_PARSE_MASK=0 when the
+                                    * context is created: no such buffer */
   int32_t device;                  /* HIP device ordinal */
   uint32_t shard_index;            /* this context owns quotients [shard_index, shard_index+1) * 2^qb / num_shards */
   uint32_t num_shards;             /* 0 or 1 = whole filter; otherwise a power of two */

@@ -40,26 +40,29 @@ __device__ __forceinline__ uint32_t shk_nl_flags(uint32_t w) {
   return ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x | 0x7F7F7F7Fu);
 }
 
+// Clears, in the per-word newline flags w[0..4) of the 16-byte unit at byte b0, the flags of bytes outside [off, end).
+__device__ __forceinline__ void shk_clip_flags(uint32_t w[4], uint64_t b0, uint64_t off, uint64_t end) {
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    uint64_t wb = b0 + 4 * i;
+    if (wb < off || wb + 4 > end) {
+#pragma unroll
+      for (int j = 0; j < 4; j++)
+        if (wb + j < off || wb + j >= end) w[i] &= ~(0x80u << (8 * j));
+    }
+  }
+}
 // Loads the 16-byte unit `u` of a chunk (units are 16-B aligned in the text buffer) and
 // returns per-word newline flags with bytes outside [off, off+len) masked away.
 __device__ __forceinline__ uint4 shk_unit_flags(const uint8_t *text, uint64_t a0, uint64_t u, uint64_t off,
                                                 uint64_t end) {
   const uint4 v = *reinterpret_cast<const uint4 *>(text + a0 + 16 * u);
-  uint32_t w[4] = {v.x, v.y, v.z, v.w};
-  uint64_t b0 = a0 + 16 * u;
-#pragma unroll
-  for (int i = 0; i < 4; i++) {
-    uint32_t f = shk_nl_flags(w[i]);
-    uint64_t wb = b0 + 4 * i;
-    if (wb < off || wb + 4 > end) {
-#pragma unroll
-      for (int j = 0; j < 4; j++)
-        if (wb + j < off || wb + j >= end) f &= ~(0x80u << (8 * j));
-    }
-    w[i] = f;
-  }
+  uint32_t w[4] = {shk_nl_flags(v.x), shk_nl_flags(v.y), shk_nl_flags(v.z), shk_nl_flags(v.w)};
+  shk_clip_flags(w, a0 + 16 * u, off, end);
   return make_uint4(w[0], w[1], w[2], w[3]);
 }
+// the four flags of a word (0x80 in bytes 0..3) as bits 0..3: the partial products land on distinct bits, no carries
+__device__ __forceinline__ uint32_t shk_flags_to_bits(uint32_t f) { return ((f >> 7) * 0x01020408u) >> 24; }
 
 // ---------------------------------------------------------------- lines per chunk
 // A chunk (8 MiB) is cut into SHK_PARSE_SEGS segments of whole 16-byte units; one workgroup per
@@ -71,8 +74,11 @@ __device__ __forceinline__ void shk_segment_units(uint64_t nunits, unsigned seg,
   *u1 = *u0 + per < nunits ? *u0 + per : nunits;
 }
 
+// nlmask (may be null): the newline flags of every unit the chunk's segments cover, one uint16_t per 16-byte unit of the
+// text at index (byte offset from the text's base) / 16, bit j = byte j of the unit is '\n'. NOT clipped to the chunk: a
+// pure function of the text, so chunks that share a unit store the same value. k_emit_reads reads them instead of the text.
 __global__ void k_count_lines(const uint8_t *text, const uint64_t *chunk_off, const uint64_t *chunk_len,
-                              uint64_t *nlines_seg) {
+                              uint64_t *nlines_seg, uint16_t *nlmask) {
   __shared__ uint64_t scratch[SHK_MAX_WAVES + 1];
   const unsigned c = blockIdx.x / SHK_PARSE_SEGS, seg = blockIdx.x % SHK_PARSE_SEGS;
   const uint64_t off = chunk_off[c], end = off + chunk_len[c];
@@ -82,8 +88,14 @@ __global__ void k_count_lines(const uint8_t *text, const uint64_t *chunk_off, co
   shk_segment_units(nunits, seg, &u0, &u1);
   uint64_t cnt = 0;
   for (uint64_t u = u0 + threadIdx.x; u < u1; u += blockDim.x) {
-    uint4 f = shk_unit_flags(text, a0, u, off, end);
-    cnt += __popc(f.x) + __popc(f.y) + __popc(f.z) + __popc(f.w);
+    const uint64_t b0 = a0 + 16 * u;
+    const uint4 v = *reinterpret_cast<const uint4 *>(text + b0);
+    uint32_t w[4] = {shk_nl_flags(v.x), shk_nl_flags(v.y), shk_nl_flags(v.z), shk_nl_flags(v.w)};
+    if (nlmask)
+      nlmask[b0 >> 4] = (uint16_t)(shk_flags_to_bits(w[0]) | shk_flags_to_bits(w[1]) << 4 | shk_flags_to_bits(w[2]) << 8 |
+                                   shk_flags_to_bits(w[3]) << 12);
+    shk_clip_flags(w, b0, off, end);
+    cnt += __popc(w[0]) + __popc(w[1]) + __popc(w[2]) + __popc(w[3]);
   }
   uint64_t tot = shk_block_sum64(cnt, scratch);
   if (threadIdx.x == 0) nlines_seg[blockIdx.x] = tot;
@@ -123,19 +135,23 @@ __global__ void k_scan_chunks(uint64_t *nlines_seg, unsigned nchunks, uint64_t *
 // ---------------------------------------------------------------- sequence-line extents
 // Line l (0-based, by newline count from the chunk start) is a header when l%4==0 and
 // the read when l%4==1 -- the same strict 4-line walk as CQF_mt.h:616-726.
-__global__ void k_emit_reads(const uint8_t *text, const uint64_t *chunk_off, const uint64_t *chunk_len,
-                             const uint64_t *reads_base, const uint64_t *line_base_seg, uint64_t *rd_start, uint64_t *rd_end,
-                             uint16_t *rd_chunk) {
-  __shared__ uint32_t scratch[SHK_MAX_WAVES + 1];
-  __shared__ uint64_t line_carry;
-  const unsigned c = blockIdx.x / SHK_PARSE_SEGS, seg = blockIdx.x % SHK_PARSE_SEGS;
-  const uint64_t off = chunk_off[c], end = off + chunk_len[c];
+// line `line` of chunk c ends with the newline at byte `pos`
+__device__ __forceinline__ void shk_emit_line(uint64_t line, uint64_t pos, unsigned c, uint64_t rbase, uint64_t nreads,
+                                              uint64_t *rd_start, uint64_t *rd_end, uint16_t *rd_chunk) {
+  const uint64_t rd = line >> 2;
+  if (rd < nreads) {
+    if ((line & 3) == 0) { rd_start[rbase + rd] = pos + 1; rd_chunk[rbase + rd] = (uint16_t)c; }
+    else if ((line & 3) == 1) rd_end[rbase + rd] = pos;
+  }
+}
+
+// From the text: one 16-byte unit per thread and round, the line index at the head of a round in LDS. The form of a
+// context created with SHK_PARSE_MASK=0, and of a batch whose flags buffer could not grow.
+__device__ __forceinline__ void shk_emit_from_text(const uint8_t *text, unsigned c, uint64_t off, uint64_t end, uint64_t u0, uint64_t u1,
+                                                   uint64_t line0, uint64_t rbase, uint64_t nreads, uint64_t *rd_start,
+                                                   uint64_t *rd_end, uint16_t *rd_chunk, uint32_t *scratch, uint64_t *line_carry) {
   const uint64_t a0 = off & ~15ULL;
-  const uint64_t nunits = (end - a0 + 15) / 16;
-  uint64_t u0, u1;
-  shk_segment_units(nunits, seg, &u0, &u1);
-  const uint64_t rbase = reads_base[c], nreads = reads_base[c + 1] - rbase;
-  if (threadIdx.x == 0) line_carry = line_base_seg[blockIdx.x];
+  if (threadIdx.x == 0) *line_carry = line0;
   __syncthreads();
   for (uint64_t ub = u0; ub < u1; ub += blockDim.x) {
     uint64_t u = ub + threadIdx.x;
@@ -144,7 +160,7 @@ __global__ void k_emit_reads(const uint8_t *text, const uint64_t *chunk_off, con
     uint32_t n = __popc(f.x) + __popc(f.y) + __popc(f.z) + __popc(f.w);
     uint32_t tot;
     uint32_t ex = shk_block_exscan(n, &tot, scratch);
-    uint64_t line = line_carry + ex;
+    uint64_t line = *line_carry + ex;
     if (n) {
       uint32_t w[4] = {f.x, f.y, f.z, f.w};
 #pragma unroll
@@ -153,20 +169,80 @@ __global__ void k_emit_reads(const uint8_t *text, const uint64_t *chunk_off, con
         while (m) {
           int bit = __ffs(m) - 1;  // 7, 15, 23 or 31
           m &= m - 1;
-          uint64_t pos = a0 + 16 * u + 4 * i + (bit >> 3);
-          uint64_t rd = line >> 2;
-          if (rd < nreads) {
-            if ((line & 3) == 0) { rd_start[rbase + rd] = pos + 1; rd_chunk[rbase + rd] = (uint16_t)c; }
-            else if ((line & 3) == 1) rd_end[rbase + rd] = pos;
-          }
-          line++;
+          shk_emit_line(line++, a0 + 16 * u + 4 * i + (bit >> 3), c, rbase, nreads, rd_start, rd_end, rd_chunk);
         }
       }
     }
     __syncthreads();
-    if (threadIdx.x == 0) line_carry += tot;
+    if (threadIdx.x == 0) *line_carry += tot;
     __syncthreads();
   }
+}
+
+// From the flags k_count_lines left (one bit per text byte): a thread takes a group of 8 consecutive units, aligned by
+// ABSOLUTE unit index, with one 16-byte load = 128 bytes of text, so a segment of 512 KiB is 8 rounds of a 512-thread
+// workgroup, one scan each, against 64 rounds over the text. Chunks start on any residue mod 128: the first and last group
+// of a segment are partial, and their flags outside [lo, hi) = the segment's units cut to the chunk's bytes are cleared
+// (the same rule as shk_clip_flags: byte b counts when lo <= b < hi). Flags of units that no chunk covers may be read
+// here (never written: whatever they hold is cleared); the buffer has 8 units of room behind the text's last unit.
+__device__ __forceinline__ void shk_emit_from_flags(const uint16_t *nlmask, unsigned c, uint64_t off, uint64_t end, uint64_t u0, uint64_t u1,
+                                                    uint64_t line0, uint64_t rbase, uint64_t nreads, uint64_t *rd_start,
+                                                    uint64_t *rd_end, uint16_t *rd_chunk, uint32_t *scratch) {
+  if (u0 >= u1) return;                      // (uniform: an empty segment)
+  const uint64_t a0 = off & ~15ULL;
+  const uint64_t lo = u0 ? a0 + 16 * u0 : off;                       // bytes [lo, hi) are this segment's
+  const uint64_t hi = a0 + 16 * u1 < end ? a0 + 16 * u1 : end;
+  const uint64_t stride = (uint64_t)blockDim.x * 128;
+  for (uint64_t gb = (lo & ~127ULL); gb < hi; gb += stride) {
+    const uint64_t g = gb + (uint64_t)threadIdx.x * 128;            // first byte of this thread's group
+    uint32_t w[4] = {0, 0, 0, 0};                                    // bit b of the 128 = byte g + b is a newline
+    if (g < hi) {
+      const uint4 v = *reinterpret_cast<const uint4 *>(nlmask + (g >> 4));
+      w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+      if (g < lo || g + 128 > hi) {
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+          const uint64_t wb = g + 32 * i;
+          const uint32_t below_lo = wb >= lo ? 0u : lo - wb >= 32 ? 0xFFFFFFFFu : (1u << (uint32_t)(lo - wb)) - 1u;
+          const uint32_t below_hi = wb >= hi ? 0u : hi - wb >= 32 ? 0xFFFFFFFFu : (1u << (uint32_t)(hi - wb)) - 1u;
+          w[i] &= below_hi & ~below_lo;
+        }
+      }
+    }
+    const uint32_t n = __popc(w[0]) + __popc(w[1]) + __popc(w[2]) + __popc(w[3]);
+    uint32_t tot;
+    const uint32_t ex = shk_block_exscan(n, &tot, scratch);
+    uint64_t line = line0 + ex;
+    if (n) {
+#pragma unroll
+      for (int i = 0; i < 4; i++) {
+        uint32_t m = w[i];
+        while (m) {
+          const int bit = __ffs(m) - 1;
+          m &= m - 1;
+          shk_emit_line(line++, g + 32 * i + bit, c, rbase, nreads, rd_start, rd_end, rd_chunk);
+        }
+      }
+    }
+    line0 += tot;                            // (every thread keeps the line index at the head of the round: the scan gives all of them its total)
+  }
+}
+
+// nlmask: k_count_lines' flags of this text, or null = read the text itself
+__global__ void k_emit_reads(const uint8_t *text, const uint16_t *nlmask, const uint64_t *chunk_off, const uint64_t *chunk_len,
+                             const uint64_t *reads_base, const uint64_t *line_base_seg, uint64_t *rd_start, uint64_t *rd_end,
+                             uint16_t *rd_chunk) {
+  __shared__ uint32_t scratch[SHK_MAX_WAVES + 1];
+  __shared__ uint64_t line_carry;
+  const unsigned c = blockIdx.x / SHK_PARSE_SEGS, seg = blockIdx.x % SHK_PARSE_SEGS;
+  const uint64_t off = chunk_off[c], end = off + chunk_len[c];
+  const uint64_t nunits = (end - (off & ~15ULL) + 15) / 16;
+  uint64_t u0, u1;
+  shk_segment_units(nunits, seg, &u0, &u1);
+  const uint64_t rbase = reads_base[c], nreads = reads_base[c + 1] - rbase;
+  const uint64_t line0 = line_base_seg[blockIdx.x];
+  if (nlmask) shk_emit_from_flags(nlmask, c, off, end, u0, u1, line0, rbase, nreads, rd_start, rd_end, rd_chunk, scratch);
+  else shk_emit_from_text(text, c, off, end, u0, u1, line0, rbase, nreads, rd_start, rd_end, rd_chunk, scratch, &line_carry);
 }
 
 // ---------------------------------------------------------------- the 'N' restart rule

@@ -107,6 +107,8 @@ struct ShkStageBufs {
   uint64_t *d_chunk_off = nullptr, *d_chunk_len = nullptr, *d_nlines = nullptr, *d_reads_base = nullptr;
   uint64_t *d_rd_start = nullptr, *d_rd_end = nullptr;
   uint16_t *d_rd_chunk = nullptr;         // chunk (within the call) of every read
+  uint16_t *d_nlmask = nullptr;           // newline flags of the text in hand, one word per 16-byte unit (k_count_lines -> k_emit_reads);
+  uint64_t nlmask_units = 0;              // its capacity. Null in a context created with SHK_PARSE_MASK=0; parse_stage grows it
   uint32_t *d_nkeys = nullptr;
   uint64_t *d_key_base = nullptr;
   uint64_t *d_words[2] = {};
@@ -148,6 +150,7 @@ struct shk_ctx : ShkStageBufs {
   ShkPartLevel part[4];         // the partition plan, level by level
   bool roll_two;                // roll_stage's histogram pass counts the first two levels' digits together (they fit its LDS bins)
   bool roll_slots;              // three levels, all slotted: a narrow batch of text runs without any counting pass (roll_stage)
+  bool parse_mask;              // k_count_lines keeps the newline flags and k_emit_reads reads them, not the text (parse_stage)
   uint32_t threads, hash_groups;
   // state
   uint64_t nelts, ndistinct;
@@ -274,6 +277,15 @@ static uint64_t level_out(const shk_ctx *c, uint32_t l) { return (uint64_t)c->lv
 // (128 slots of a 6.5 M share: 837.5 M words for 832 M keys)
 static uint64_t words_cap(const shk_ctx *c) { return c->cfg.max_batch_keys + (c->roll_slots ? c->cfg.max_batch_keys / 64 : 0); }
 
+// (exactly `units` words, without dmalloc's slack: the 8 units of room behind the text's last unit are part of the count)
+static int nlmask_alloc(ShkStageBufs *b, uint64_t units) {
+  void *v = nullptr;
+  if (hipMalloc(&v, units * sizeof(uint16_t)) != hipSuccess) { (void)hipGetLastError(); return SHK_ERR_HIP; }
+  b->d_nlmask = (uint16_t *)v;
+  b->nlmask_units = units;
+  return 0;
+}
+
 static int bufs_alloc(const shk_ctx *c, ShkStageBufs *b, bool lent) {
   const uint64_t capk = c->cfg.max_batch_keys;
   const uint32_t maxch = SHK_MAX_CHUNKS;
@@ -283,6 +295,12 @@ static int bufs_alloc(const shk_ctx *c, ShkStageBufs *b, bool lent) {
   if (lent) HIPCHK(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
   else HIPCHK(hipStreamCreate(&b->stream));
   if (dmalloc(&b->d_text, c->cfg.max_batch_bytes + 64)) return SHK_ERR_HIP;
+  // Host text is at most max_batch_bytes; device text has no configured bound: four text bytes per key cover ordinary
+  // short-read FASTQ, so that a fresh context's first batch allocates nothing (parse_stage grows the buffer otherwise)
+  if (c->parse_mask) {
+    const uint64_t tb = c->cfg.max_batch_bytes > 4 * capk ? c->cfg.max_batch_bytes : 4 * capk;
+    if (nlmask_alloc(b, tb / 16 + 8)) return SHK_ERR_HIP;
+  }
   if (dmalloc(&b->d_chunk_off, maxch) || dmalloc(&b->d_chunk_len, maxch) || dmalloc(&b->d_nlines, (uint64_t)maxch * SHK_PARSE_SEGS) ||
       dmalloc(&b->d_reads_base, maxch + 1)) return SHK_ERR_HIP;
   if (dmalloc(&b->d_rd_start, c->max_reads + 1) || dmalloc(&b->d_rd_end, c->max_reads + 1) ||
@@ -322,6 +340,7 @@ static void bufs_free(const shk_ctx *c, ShkStageBufs *b) {
   for (size_t i = 0; i < b->evpool.size(); i++) hipEventDestroy(b->evpool[i]);
   b->evpool.clear();
   hipFree(b->d_text); hipFree(b->d_chunk_off); hipFree(b->d_chunk_len); hipFree(b->d_nlines); hipFree(b->d_reads_base);
+  hipFree(b->d_nlmask);
   hipFree(b->d_rd_start); hipFree(b->d_rd_end); hipFree(b->d_rd_chunk); hipFree(b->d_nkeys); hipFree(b->d_key_base); hipFree(b->d_scalars);
   hipFree(b->d_block_sums); hipFree(b->d_base_sub); hipFree(b->d_cursor); hipFree(b->d_end[1]); hipFree(b->d_end[2]); hipFree(b->d_tfb); hipFree(b->d_err);
   if (!b->lent) { hipFree(b->d_words[0]); hipFree(b->d_words[1]); }
@@ -391,6 +410,8 @@ static int create_init(shk_ctx *c, const shk_config *cfg) {
   c->roll_slots = c->nlevels == 3 && c->part[1].may_narrow && c->part[2].may_slot &&
                   !(getenv("SHK_ROLL_SLOTS") && atoi(getenv("SHK_ROLL_SLOTS")) == 0) &&
                   cfg->max_batch_keys / (level_out(c, 1)) >= 28800;
+  // SHK_PARSE_MASK=0: k_emit_reads reads the text again
+  c->parse_mask = !(getenv("SHK_PARSE_MASK") && atoi(getenv("SHK_PARSE_MASK")) == 0);
   c->rounds_left = cfg->num_denoise;
   c->max_reads = cfg->max_batch_reads ? cfg->max_batch_reads : cfg->max_batch_bytes / 16 + 1024;
   { int rc = bufs_alloc(c, c, false); if (rc) return rc; }
@@ -529,20 +550,35 @@ static bool text_aligned(const void *text, int on_device) { return !on_device ||
 static int parse_stage(const shk_ctx *c, ShkStageBufs *b, const void *text, int on_device, uint64_t text_bytes, const uint64_t *chunk_off,
                        const uint64_t *chunk_len, uint32_t nchunks, const uint8_t **dtext_out, uint64_t *nreads_out) {
   if (!text_aligned(text, on_device)) return SHK_ERR_ARG;
-  for (uint32_t i = 0; i < nchunks; i++)
+  uint64_t text_end = 0;
+  for (uint32_t i = 0; i < nchunks; i++) {
     if (chunk_off[i] + chunk_len[i] > text_bytes) return SHK_ERR_ARG;
+    if (chunk_off[i] + chunk_len[i] > text_end) text_end = chunk_off[i] + chunk_len[i];
+  }
+  if (!on_device && text_bytes > c->cfg.max_batch_bytes) return SHK_ERR_BATCH;
+  // The flags of every unit up to the last chunk's end, and 8 units of room for k_emit_reads' groups of 8. A text beyond the
+  // capacity (device text of more than four bytes per key) gets a larger buffer, never a smaller one; when that allocation
+  // fails the batch runs on the text-reading emitter
+  const uint64_t mask_units = text_end / 16 + 8;
+  if (c->parse_mask && mask_units > b->nlmask_units) {
+    HIPCHK(hipStreamSynchronize(b->stream));
+    hipFree(b->d_nlmask);
+    b->d_nlmask = nullptr;
+    b->nlmask_units = 0;
+    (void)nlmask_alloc(b, mask_units);
+  }
+  uint16_t *const nlmask = c->parse_mask && mask_units <= b->nlmask_units ? b->d_nlmask : nullptr;
   const uint8_t *dtext;
   if (on_device) {
     dtext = (const uint8_t *)text;
   } else {
-    if (text_bytes > c->cfg.max_batch_bytes) return SHK_ERR_BATCH;
     HIPCHK(hipMemcpyAsync(b->d_text, text, text_bytes, hipMemcpyHostToDevice, b->stream));
     dtext = b->d_text;
   }
   HIPCHK(hipMemcpyAsync(b->d_chunk_off, chunk_off, nchunks * 8, hipMemcpyHostToDevice, b->stream));
   HIPCHK(hipMemcpyAsync(b->d_chunk_len, chunk_len, nchunks * 8, hipMemcpyHostToDevice, b->stream));
   { ProfScope ps(c, b, KP_COUNT_LINES);
-    hipLaunchKernelGGL(k_count_lines, dim3(nchunks * SHK_PARSE_SEGS), dim3(c->threads), 0, b->stream, dtext, b->d_chunk_off, b->d_chunk_len, b->d_nlines); }
+    hipLaunchKernelGGL(k_count_lines, dim3(nchunks * SHK_PARSE_SEGS), dim3(c->threads), 0, b->stream, dtext, b->d_chunk_off, b->d_chunk_len, b->d_nlines, nlmask); }
   { ProfScope ps(c, b, KP_SCAN_CHUNKS);
     hipLaunchKernelGGL(k_scan_chunks, dim3(1), dim3(c->threads), 0, b->stream, b->d_nlines, nchunks, b->d_reads_base, b->d_scalars + DS_NREADS); }
   // the read arrays are sized by max_reads: the count is checked on the host below
@@ -551,7 +587,7 @@ static int parse_stage(const shk_ctx *c, ShkStageBufs *b, const void *text, int 
   const uint64_t nreads = b->h_pinned[HP_NREADS];
   if (nreads > c->max_reads) return SHK_ERR_BATCH;
   { ProfScope ps(c, b, KP_EMIT_READS);
-    hipLaunchKernelGGL(k_emit_reads, dim3(nchunks * SHK_PARSE_SEGS), dim3(c->threads), 0, b->stream, dtext, b->d_chunk_off, b->d_chunk_len,
+    hipLaunchKernelGGL(k_emit_reads, dim3(nchunks * SHK_PARSE_SEGS), dim3(c->threads), 0, b->stream, dtext, (const uint16_t *)nlmask, b->d_chunk_off, b->d_chunk_len,
                        b->d_reads_base, b->d_nlines, b->d_rd_start, b->d_rd_end, b->d_rd_chunk); }
   *dtext_out = dtext;
   *nreads_out = nreads;
