@@ -32,6 +32,7 @@
  *   shk_intersect         qf_intersect                                      cqf/gqf.c:2736-2757
  *   shk_magnitude         qf_magnitude                                      cqf/gqf.c:2760-2763
  *   shk_spectrum          (no counterpart: the reference's README sends the user to an outside program for F0, F1, f1, f2, ...)
+ *   shk_count_fasta       (no counterpart: the reference reads 4-line FASTQ only, cqf/CQF_mt.h:610-731) FASTA text of any shape
  *   shk_import_shards     (no counterpart: the reference is one process) quotient-range shards -> the single table
  *   shk_stats             runtime->nelts / ndistinct_elts / num_deNoise    cqf/CQF_mt.h:277-288
  *   shk_destroy           CQF_mt::~CQF_mt -> qf_destroy                    cqf/CQF_mt.h:547-557; gqf.c:2306
@@ -83,7 +84,10 @@ typedef struct shk_config {
                                     * bytes (+ 16), once more in a context that has used shk_prepare_chunks. Device text of more
                                     * than four bytes per key makes a call grow them to text_bytes / 8 (never back); if that
                                     * allocation fails the call reads the text a second time instead. SHK_PARSE_MASK=0 when the
-                                    * context is created: no such buffer */
+                                    * context is created: no such buffer.
+                                    * The first shk_count_fasta allocates its own: max_batch_bytes / 4 bytes for the piece's bases at
+                                    * 2 bits each, max_batch_bytes / 16 for the state in front of every 16 text bytes, and about 70 bytes
+                                    * per tile of 4 KiB of text; they stay until shk_destroy */
   int32_t device;                  /* HIP device ordinal */
   uint32_t shard_index;            /* this context owns quotients [shard_index, shard_index+1) * 2^qb / num_shards */
   uint32_t num_shards;             /* 0 or 1 = whole filter; otherwise a power of two */
@@ -168,6 +172,37 @@ int shk_hash_chunks(shk_ctx *ctx, const void *text, int text_on_device, uint64_t
  * quotient range). nchunks = 1 + the largest chunk index present. */
 int shk_count_words(shk_ctx *ctx, const uint64_t *d_words, uint64_t nwords, uint32_t nchunks,
                     shk_batch_stats *stats);
+
+/* ---- FASTA (no counterpart in the reference). Counts the k-mers of FASTA text: records and lines of any length, one or
+ * many records, with or without headers.
+ *   - A line whose first byte is '>' or ';' is a header line: nothing in it is sequence, whatever it holds, however long.
+ *   - In every other line '\n' and '\r' are skipped, A C G T a c g t are bases, and every other byte is a BREAK: N, the
+ *     IUPAC codes, space, tab, '*', '-', NUL, bytes >= 0x80, a '>' that is not at a line start. A header line is a break
+ *     too. Text that starts without a header is sequence.
+ *   - A k-mer is counted exactly when its k bases follow each other with nothing but line ends between them. Its key is
+ *     the one the FASTQ path gives the same k-mer: canonical ntHash masked to hb bits. For reads made of bases only, FASTA
+ *     and FASTQ input therefore give identical tables; they differ only where reads_to_kmers hashes windows that hold a
+ *     byte that is no base (the first window of a read, and the one behind an 'N'): this path never hashes such a window.
+ *   - No limit on the length of a record or a line: a run of bases is cut into segments of SHK_FASTA_SEGMENT k-mers, one
+ *     per device thread, which overlap by k - 1 bases.
+ * Streaming: consecutive calls are consecutive pieces of ONE stream, cut at any byte (inside a header, between '\r' and
+ * '\n', in the middle of a run). The context keeps what the next piece needs: inside a header or not, at a line start or
+ * not, whether a break lies behind the last base, and the last <= k - 1 bases of the open run (on the device). first != 0
+ * forgets that state: the piece is the start of a file. A k-mer is counted by the call that brings its last base; the table
+ * after any sequence of pieces is the table after the whole text in one call.
+ * To the table a call is ONE chunk: it behaves as shk_count_words on the call's keys with nchunks = 1 (counters, `stats`,
+ * the deNoise trigger tested once, behind the call). fstats (may be NULL): records = header lines begun in this piece,
+ * bases, breaks = break BYTES outside header lines (a header counts as a record, not here), kmers = stats->kmers.
+ * Errors leave the table and the streaming state as they were, so the call can be repeated with a smaller piece:
+ * SHK_ERR_BATCH for text_bytes > max_batch_bytes, more than max_batch_keys k-mers, more segments than max_batch_reads (its
+ * default: max_batch_bytes / 16 + 1024), more runs of bases (of any length) than max_batch_keys - 2, more 64-base units of
+ * segments than max_batch_keys / 2 - 1, or batches prepared and not yet counted; SHK_ERR_ARG for a sharded context or
+ * device text that is not 16-byte aligned (the text contract of shk_count_chunks). 1 <= k <= 191, every geometry. */
+#define SHK_FASTA_SEGMENT 256    /* k-mers one device thread hashes of a long run; SHK_FASTA_SEGMENT=n in the
+                                    environment of shk_create overrides it (16 <= n, n + k - 1 <= 65535): tests */
+typedef struct shk_fasta_stats { uint64_t records, bases, breaks, kmers; } shk_fasta_stats;
+int shk_count_fasta(shk_ctx *ctx, const void *text, int text_on_device, uint64_t text_bytes, int first,
+                    shk_batch_stats *stats, shk_fasta_stats *fstats /* may be NULL */);
 
 /* ---- staged form of shk_count_words for several GPUs. The deNoise trigger is a property of
  * the WHOLE filter, so with quotient-range shards the host reduces each shard's statistics

@@ -23,17 +23,18 @@
 #include "merge2_kernels.hip"
 #include "walk_kernels.hip"
 #include "unitig_kernels.hip"
+#include "fasta_kernels.hip"
 
 #define SHK_SLACK 256  // bytes of slack behind buffers read with wide loads
 
 enum {
   KP_COUNT_LINES, KP_SCAN_CHUNKS, KP_EMIT_READS, KP_COUNT_KEYS, KP_HASH, KP_SCAN, KP_RP_PREP, KP_RP_HIST,
-  KP_RP_SCATTER, KP_MERGE_SUM, KP_REGION_SCAN, KP_MERGE_WRITE, KP_MERGE_SPILL, KP_PLACE, KP_MARKS, KP_LOOKUP, KP_WALK, KP_UG_WALK, KP_UG_FINISH, KP_MERGE_FUSED, KP_MERGE_SAMPLE, KP_MISC, KP_ROLL_HIST, KP_ROLL_SCATTER, KP_PACK, KP_RP_SLOTS, KP_RP_SCATTER_NARROW, KP_SPECTRUM, KP_JOIN, KP_N
+  KP_RP_SCATTER, KP_MERGE_SUM, KP_REGION_SCAN, KP_MERGE_WRITE, KP_MERGE_SPILL, KP_PLACE, KP_MARKS, KP_LOOKUP, KP_WALK, KP_UG_WALK, KP_UG_FINISH, KP_MERGE_FUSED, KP_MERGE_SAMPLE, KP_MISC, KP_ROLL_HIST, KP_ROLL_SCATTER, KP_PACK, KP_RP_SLOTS, KP_RP_SCATTER_NARROW, KP_SPECTRUM, KP_JOIN, KP_FA_MAPS, KP_FA_STATES, KP_FA_COUNT, KP_FA_COMPACT, KP_FA_SEGMENTS, KP_FA_PACK, KP_N
 };
 static const char *kp_names[KP_N] = {
   "k_count_lines", "k_scan_chunks", "k_emit_reads", "k_count_keys", "k_hash_reads", "k_scan_*", "k_rp_prep",
   "k_rp_hist", "k_rp_scatter", "k_region_merge<summary>", "k_region_scan", "k_region_merge<write>",
-  "k_region_merge<spill>", "k_region_place", "k_denoise_marks", "k_lookup", "k_extend_forward+k_select_seeds", "k_ug_walk", "k_ug_check/emit/median/links", "k_region_merge<fused>", "k_region_merge<sample>", "misc", "k_roll_hist", "k_roll_scatter", "k_pack_reads", "k_rp_slot_cursors", "k_rp_scatter<narrow>", "k_region_spectrum", "k_region_join"};
+  "k_region_merge<spill>", "k_region_place", "k_denoise_marks", "k_lookup", "k_extend_forward+k_select_seeds", "k_ug_walk", "k_ug_check/emit/median/links", "k_region_merge<fused>", "k_region_merge<sample>", "misc", "k_roll_hist", "k_roll_scatter", "k_pack_reads", "k_rp_slot_cursors", "k_rp_scatter<narrow>", "k_region_spectrum", "k_region_join", "k_fa_maps", "k_fa_states", "k_fa_count", "k_fa_compact", "k_fa_segments+long+tail", "k_fa_pack"};
 
 struct PendingEvent { int id; hipEvent_t a, b; };
 
@@ -201,6 +202,8 @@ struct shk_ctx : ShkStageBufs {
   uint64_t *d_send[2];          // shk_route_words: two alternating send buffers (allocated on first use), so that the
   int send_next;                // exchange of one batch can run while the next batch is hashed and routed
   struct ShkFront *front;       // shk_prepare_chunks: the front end (parse, hash, partition) of later batches on its own stream
+  struct ShkFasta *fasta;       // shk_count_fasta: its buffers and the state of the stream (allocated by the first call)
+  uint32_t fasta_seg;           // k-mers per segment there (SHK_FASTA_SEGMENT)
 };
 
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "libshk: %s failed: %s (%s:%d)\n", #x, hipGetErrorString(e_), __FILE__, __LINE__); return SHK_ERR_HIP; } } while (0)
@@ -412,6 +415,12 @@ static int create_init(shk_ctx *c, const shk_config *cfg) {
                   cfg->max_batch_keys / (level_out(c, 1)) >= 28800;
   // SHK_PARSE_MASK=0: k_emit_reads reads the text again
   c->parse_mask = !(getenv("SHK_PARSE_MASK") && atoi(getenv("SHK_PARSE_MASK")) == 0);
+  c->fasta_seg = SHK_FASTA_SEGMENT;
+  if (const char *e = getenv("SHK_FASTA_SEGMENT")) {
+    const long v = atol(e);
+    if (v < 16 || v + cfg->k - 1 > 65535) return SHK_ERR_ARG;
+    c->fasta_seg = (uint32_t)v;
+  }
   c->rounds_left = cfg->num_denoise;
   c->max_reads = cfg->max_batch_reads ? cfg->max_batch_reads : cfg->max_batch_bytes / 16 + 1024;
   { int rc = bufs_alloc(c, c, false); if (rc) return rc; }
@@ -469,10 +478,12 @@ extern "C" int shk_create(const shk_config *cfg, shk_ctx **out) {
 
 // (of a partly built context too: shk_create comes here from every failure)
 static void front_destroy(shk_ctx *c);
+static void fasta_destroy(shk_ctx *c);
 extern "C" void shk_destroy(shk_ctx *c) {
   if (!c) return;
   hipSetDevice(c->dev);
   front_destroy(c);
+  fasta_destroy(c);
   if (c->stream) hipStreamSynchronize(c->stream);
   if (c->copy_stream) {
     hipStreamSynchronize(c->copy_stream);
@@ -695,6 +706,7 @@ static uint64_t up_slot_capacity(double m, uint64_t unit) {
 struct ShkRollBatch {
   const uint8_t *dtext; uint64_t text_bytes, nreads;
   uint32_t nchunks, chunk_first, chunk_mul;
+  bool staged;          // every read lies in 2-bit units already (shk_count_fasta): d_words[1], d_key_base and d_nkeys are as pack_stage leaves them
 };
 
 // The roll kernels over a parsed batch, from the 2-bit staging on. slots: no histogram pass; digit d owns the slot
@@ -725,7 +737,8 @@ static int roll_keys(const shk_ctx *c, ShkStageBufs *b, const ShkRollBatch &R, b
   A.hist = two ? b->d_hist[1] : b->d_hist[0]; A.hist_shift = two ? c->lv[1].shift : c->lv[0].shift; A.hist_bits = two ? cb : c->lv[0].bits;
   A.cursor = b->d_cursor; A.out = b->d_words[0];
   if (cap0) A.cap = P * cap0;
-  { int rc = pack_stage(c, b, A, R.nreads, R.text_bytes, b->d_words[1]); if (rc) return rc; }     // (d_words[1]: the partition's other buffer, idle until its second level)
+  if (R.staged) { A.pk = (const ShkQuad *)b->d_words[1]; A.pk_base = b->d_key_base; A.pk_flag = b->d_nkeys; }
+  else { int rc = pack_stage(c, b, A, R.nreads, R.text_bytes, b->d_words[1]); if (rc) return rc; }     // (d_words[1]: the partition's other buffer, idle until its second level)
   if (cap0) {
     launch_roll_scatter(c, b, A, R.nreads);
     ProfScope ps(c, b, KP_RP_PREP);
@@ -1864,6 +1877,174 @@ extern "C" int shk_count_words(shk_ctx *c, const uint64_t *d_words, uint64_t nwo
   rc = merge_stage(c, c->d_words[dst], nchunks, nwords, &st);
   if (stats) *stats = st;
   return finish(c, rc);
+}
+
+// ------------------------------------------------------------------ FASTA front end (fasta_kernels.hip)
+// What shk_count_fasta keeps besides the context's buffers. Of those it borrows d_text (host text), d_words[0] (the list of
+// run starts, until the roll kernels write their keys there), d_words[1] (the segments' 2-bit units, where pack_stage
+// puts a FASTQ batch's) and the read arrays (one "read" per segment).
+struct ShkFasta {
+  uint32_t *stream = nullptr;       // the piece's bases behind the tail, 2 bits each
+  uint64_t stream_words = 0;
+  uint8_t *unit_state = nullptr;    // the state in front of every 16 text bytes
+  uint32_t *tile_map = nullptr, *tile_state = nullptr;
+  uint64_t *tile_cnt = nullptr, *tile_off = nullptr;
+  uint64_t *long_runs = nullptr;    // k_fa_segments -> k_fa_long_segments: one record per run of many segments
+  uint64_t cap_long = 0;
+  uint64_t *counters = nullptr;     // [FA_NCOUNTERS] on the device
+  uint64_t *h = nullptr;            // pinned: [0, FA_NCOUNTERS) the counters read back, [FA_NCOUNTERS] the scan's total
+  ShkQuad *tail[2] = {};            // the open run's last <= k - 1 bases (three units); tail[cur] is the committed one
+  int cur = 0;
+  uint32_t state = SHK_FA_STATE_START;
+  uint64_t tail_len = 0;
+};
+static uint32_t fasta_threads(const shk_ctx *c) { return c->threads < 256 ? c->threads : 256; }
+static void fasta_destroy(shk_ctx *c);
+static int fasta_alloc(shk_ctx *c);
+static int fasta_init(shk_ctx *c) {
+  if (c->fasta) return SHK_OK;
+  const int rc = fasta_alloc(c);
+  if (rc) fasta_destroy(c);      // (the next call tries again)
+  return rc;
+}
+static int fasta_alloc(shk_ctx *c) {
+  ShkFasta *F = new ShkFasta();
+  c->fasta = F;
+  const uint64_t nb = c->cfg.max_batch_bytes, ntiles = nb / (16 * fasta_threads(c)) + 2;
+  F->stream_words = (nb + 192) / 16 + 16;     // (two quads of room behind the last base: shk_fa_unit loads a unit's neighbour)
+  if (dmalloc(&F->stream, F->stream_words) || dmalloc(&F->unit_state, nb / 16 + 2) || dmalloc(&F->tile_map, ntiles) || dmalloc(&F->tile_state, ntiles) ||
+      dmalloc(&F->tile_cnt, ntiles) || dmalloc(&F->tile_off, ntiles + 1) || dmalloc(&F->counters, FA_NCOUNTERS) || dmalloc(&F->tail[0], 3) ||
+      dmalloc(&F->tail[1], 3)) return SHK_ERR_HIP;
+  F->cap_long = ntiles;
+  if (dmalloc(&F->long_runs, SHK_FA_LONG_WORDS * F->cap_long)) return SHK_ERR_HIP;
+  HIPCHK(hipHostMalloc((void **)&F->h, (FA_NCOUNTERS + 1) * sizeof(uint64_t), hipHostMallocDefault));
+  return SHK_OK;
+}
+static void fasta_destroy(shk_ctx *c) {
+  ShkFasta *F = c->fasta;
+  if (!F) return;
+  if (c->stream) hipStreamSynchronize(c->stream);
+  hipFree(F->stream); hipFree(F->unit_state); hipFree(F->tile_map); hipFree(F->tile_state); hipFree(F->tile_cnt); hipFree(F->tile_off);
+  hipFree(F->counters); hipFree(F->tail[0]); hipFree(F->tail[1]); hipFree(F->long_runs);
+  hipHostFree(F->h);
+  delete F;
+  c->fasta = nullptr;
+}
+
+// The piece's segments -> key words partitioned by region in d_words[*dst]. Two levels and more: roll_keys behind
+// pack_stage, with counted bases. One level (roll_path() is false): the same scatter kernel with a single digit leaves the
+// words in d_words[0], and they go through the partition as a caller's words do.
+static int fasta_keys(shk_ctx *c, uint64_t nseg, uint64_t nkmers, int *dst) {
+  if (!nseg) return partition_words(c, c->d_words[0], 0, dst);
+  c->h_pinned[HP_NREADS] = nseg;
+  HIPCHK(hipMemcpyAsync(c->d_scalars + DS_NREADS, c->h_pinned + HP_NREADS, 8, hipMemcpyHostToDevice, c->stream));
+  ShkRollBatch R = {};
+  R.nreads = nseg; R.nchunks = 1; R.chunk_mul = 1; R.staged = true;
+  if (roll_path(c)) {
+    { int rc = roll_keys(c, c, R, false); if (rc) return rc; }
+    uint32_t bits = 0;
+    HIPCHK(hipMemcpyAsync(c->h_pinned + HP_NWORDS, c->d_scalars + DS_NWORDS, 8, hipMemcpyDeviceToHost, c->stream));
+    if (fetch_err(c, &bits)) return SHK_ERR_HIP;
+    if (bits) return map_err_bits(bits);
+    if (c->h_pinned[HP_NWORDS] != nkmers) return SHK_ERR_CORRUPT;
+    const int rc = partition_stage(c, c, part_from_roll(c, c, nkmers, 1), dst);
+    return rc == SHK_RC_REDO_UP ? SHK_ERR_CORRUPT : rc;
+  }
+  ShkRollArgs A;
+  roll_args(c, c, A, nullptr, 0, 0, 1);
+  A.q_lo = c->q_lo; A.dig_shift = 0; A.dig_bits = 0; A.hist = nullptr; A.hist_shift = 0; A.hist_bits = 0;
+  A.cursor = c->d_cursor; A.out = c->d_words[0];
+  A.pk = (const ShkQuad *)c->d_words[1]; A.pk_base = c->d_key_base; A.pk_flag = c->d_nkeys;
+  HIPCHK(hipMemsetAsync(c->d_cursor, 0, 8, c->stream));
+  launch_roll_scatter(c, c, A, nseg);
+  HIPCHK(hipGetLastError());
+  if (set_nwords(c, nkmers)) return SHK_ERR_HIP;
+  return partition_stage(c, c, part_from_words(c, c->d_words[0], nkmers), dst);
+}
+
+extern "C" int shk_count_fasta(shk_ctx *c, const void *text, int text_on_device, uint64_t text_bytes, int first,
+                               shk_batch_stats *stats, shk_fasta_stats *fstats) {
+  if (!c || (!text && text_bytes) || c->cfg.num_shards > 1 || !text_aligned(text, text_on_device)) return SHK_ERR_ARG;
+  if (c->front && c->front->count) return SHK_ERR_BATCH;     // (their words are partitioned against the table as it is now)
+  if (text_bytes > c->cfg.max_batch_bytes) return SHK_ERR_BATCH;
+  shk_batch_stats st;
+  memset(&st, 0, sizeof(st));
+  HIPCHK(hipSetDevice(c->dev));
+  if (upload_wait(c, text, text_on_device, c->stream)) return SHK_ERR_HIP;
+  { int rc = fasta_init(c); if (rc) return rc; }
+  ShkFasta *F = c->fasta;
+  const uint32_t st0 = first ? SHK_FA_STATE_START : F->state, k = c->cfg.k, t = fasta_threads(c);
+  const uint64_t tail = first ? 0 : F->tail_len;
+  const uint8_t *dtext = (const uint8_t *)text;
+  if (!text_on_device && text_bytes) {
+    HIPCHK(hipMemcpyAsync(c->d_text, text, text_bytes, hipMemcpyHostToDevice, c->stream));
+    dtext = c->d_text;
+  }
+  const uint64_t safe_end = (text_bytes + 15) & ~15ULL, ntiles = (text_bytes + 16 * t - 1) / (16 * t);
+  const dim3 tiles((uint32_t)(ntiles ? ntiles : 1));
+  // (a) the classes: maps, the tiles' states, counts; the tiles' bases and run starts through one scan
+  HIPCHK(hipMemsetAsync(F->counters, 0, FA_NCOUNTERS * 8, c->stream));
+  if (ntiles) { ProfScope ps(c, KP_FA_MAPS);
+    hipLaunchKernelGGL(k_fa_maps, tiles, dim3(t), 0, c->stream, dtext, text_bytes, safe_end, F->tile_map); }
+  { ProfScope ps(c, KP_FA_STATES);
+    hipLaunchKernelGGL(k_fa_states, dim3(1), dim3(c->threads), 0, c->stream, (const uint32_t *)F->tile_map, ntiles, st0, F->tile_state, F->counters + FA_END_STATE); }
+  if (ntiles) { ProfScope ps(c, KP_FA_COUNT);
+    hipLaunchKernelGGL(k_fa_count, tiles, dim3(t), 0, c->stream, dtext, text_bytes, safe_end, (const uint32_t *)F->tile_state, F->unit_state,
+                       F->tile_cnt, F->counters); }
+  if (run_scan<uint64_t>(c, c, F->tile_cnt, ntiles, nullptr, F->tile_off)) return SHK_ERR_HIP;
+  HIPCHK(hipMemcpyAsync(F->h, F->counters, FA_NCOUNTERS * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(F->h + FA_NCOUNTERS, F->tile_off + ntiles, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  const uint64_t nbases = F->h[FA_NCOUNTERS] & SHK_FA_COUNT_MASK, nruns = 1 + (F->h[FA_NCOUNTERS] >> SHK_FA_COUNT_BITS);
+  const uint64_t nbreaks = F->h[FA_NBREAK], nrec = F->h[FA_NREC];
+  const uint32_t end_state = (uint32_t)F->h[FA_END_STATE];
+  const uint64_t cap_runs = words_cap(c), cap_units = c->cfg.max_batch_keys / 2 > 1 ? c->cfg.max_batch_keys / 2 - 1 : 0;
+  if (nruns + 1 > cap_runs) { prof_collect(c); return SHK_ERR_BATCH; }
+  // (b) the stream and the run list, (c) the segments, (d) the tail
+  uint64_t *run_start = c->d_words[0];
+  { const uint64_t used = ((tail + nbases + 15) / 16 + 12) * 4;
+    HIPCHK(hipMemsetAsync(F->stream, 0, used < F->stream_words * 4 ? used : F->stream_words * 4, c->stream));
+    if (tail) HIPCHK(hipMemcpyAsync(F->stream, F->tail[F->cur], 48, hipMemcpyDeviceToDevice, c->stream)); }
+  ShkFaSegArgs S;
+  S.run_start = run_start; S.nruns = nruns; S.k = k; S.seg = c->fasta_seg;
+  S.rd_start = c->d_rd_start; S.rd_end = c->d_rd_end; S.rd_chunk = c->d_rd_chunk; S.flag = c->d_nkeys; S.pk_base = c->d_key_base;
+  S.cap_seg = c->max_reads; S.cap_units = cap_units; S.long_runs = F->long_runs; S.cap_long = F->cap_long; S.counters = F->counters; S.err = c->d_err;
+  uint64_t nseg = 0, nkmers = 0;
+  { ProfScope ps(c, KP_FA_COMPACT);
+    hipLaunchKernelGGL(k_fa_compact, tiles, dim3(t), 0, c->stream, dtext, text_bytes, safe_end, (const uint8_t *)F->unit_state, (const uint64_t *)F->tile_off,
+                       ntiles, tail, F->stream, F->stream_words, run_start, cap_runs, c->d_err); }
+  { ProfScope ps(c, KP_FA_SEGMENTS);
+    const uint64_t blocks = nruns / t + 1;
+    hipLaunchKernelGGL(k_fa_segments, dim3((uint32_t)(blocks < 2048 ? blocks : 2048)), dim3(t), 0, c->stream, S);
+    hipLaunchKernelGGL(k_fa_long_segments, dim3(c->threads < 512 ? 2 : 512), dim3(t), 0, c->stream, S);     // (small workgroups: the CPU emulator build of the tests)
+    hipLaunchKernelGGL(k_fa_tail, dim3(1), dim3(64), 0, c->stream, (const uint32_t *)F->stream, (const uint64_t *)run_start, nruns, end_state, k,
+                       F->tail[F->cur ^ 1], F->counters); }
+  HIPCHK(hipMemcpyAsync(F->h, F->counters, FA_NCOUNTERS * 8, hipMemcpyDeviceToHost, c->stream));
+  { uint32_t bits = 0;
+    if (fetch_err(c, &bits)) return SHK_ERR_HIP;
+    nseg = F->h[FA_NSEG]; nkmers = F->h[FA_NKMERS];
+    if (nkmers > c->cfg.max_batch_keys || nseg > c->max_reads || F->h[FA_NUNITS] > cap_units) { prof_collect(c); return SHK_ERR_BATCH; }
+    if (bits) { prof_collect(c); return map_err_bits(bits); } }
+  if (nseg) {
+    ProfScope ps(c, KP_FA_PACK);
+    const uint64_t pb = nseg * 4 / t + 1;
+    hipLaunchKernelGGL(k_fa_pack, dim3((uint32_t)(pb < 16384 ? pb : 16384)), dim3(t), 0, c->stream, (const uint32_t *)F->stream, nseg, (const uint64_t *)c->d_rd_start,
+                       (const uint64_t *)c->d_rd_end, (const uint64_t *)c->d_key_base, (const uint32_t *)c->d_nkeys, (ShkQuad *)c->d_words[1], cap_units, c->d_err);
+  }
+  HIPCHK(hipGetLastError());
+  const uint64_t new_tail = F->h[FA_TAIL_LEN];
+  int dst = 0;
+  int rc = fasta_keys(c, nseg, nkmers, &dst);
+  if (rc) return finish(c, rc);
+  // to the table the piece is one chunk: the trigger is tested once, behind it
+  rc = merge_stage(c, c->d_words[dst], 1, nkmers, &st);
+  rc = finish(c, rc);
+  if (rc == SHK_OK || st.chunks) {       // (the chunk is in the table: the stream has moved on, whatever a round behind it did)
+    F->cur ^= 1; F->state = end_state; F->tail_len = new_tail;
+  }
+  if (stats) *stats = st;
+  if (fstats) { fstats->records = nrec; fstats->bases = nbases; fstats->breaks = nbreaks; fstats->kmers = st.kmers; }
+  return rc;
 }
 
 // where routed words go: one of two alternating send buffers (allocated on first use)

@@ -12,6 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(os.path.dirname(_HERE), "libshk.so")
 
 MAX_CHUNKS = 4096
+FASTA_SEGMENT = 256           # SHK_FASTA_SEGMENT (include/shk.h)
 
 
 class Config(C.Structure):
@@ -39,6 +40,14 @@ class Totals(C.Structure):
 
 class SpectrumTotals(C.Structure):
     _fields_ = [("distinct", C.c_uint64), ("total", C.c_uint64), ("sumsq", C.c_uint64), ("max_count", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class FastaStats(C.Structure):
+    """shk_fasta_stats (include/shk.h)"""
+    _fields_ = [("records", C.c_uint64), ("bases", C.c_uint64), ("breaks", C.c_uint64), ("kmers", C.c_uint64)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -75,7 +84,7 @@ EXPORTS = ["shk_create", "shk_destroy", "shk_count_chunks", "shk_hash_chunks", "
            "shk_stats", "shk_header", "shk_export_blocks", "shk_export_cqf", "shk_import_cqf", "shk_import_blocks",
            "shk_lookup", "shk_profile_enable", "shk_profile_get", "shk_profile_reset", "shk_strerror",
            "shk_last_error_bits", "shk_insert_counted", "shk_dump", "shk_merge", "shk_multi_merge", "shk_import_shards", "shk_table_ptr", "shk_unitigs_add_reads",
-           "shk_spectrum", "shk_inner_product", "shk_magnitude", "shk_intersect"]
+           "shk_spectrum", "shk_inner_product", "shk_magnitude", "shk_intersect", "shk_count_fasta"]
 
 _libs = {}
 
@@ -94,6 +103,7 @@ def load(path=None):
     L.shk_destroy.argtypes = [vp]
     L.shk_destroy.restype = None
     L.shk_count_chunks.argtypes = [vp, vp, i32, u64, pu64, pu64, u32, C.POINTER(BatchStats)]
+    L.shk_count_fasta.argtypes = [vp, vp, i32, u64, i32, C.POINTER(BatchStats), C.POINTER(FastaStats)]
     L.shk_hash_chunks.argtypes = [vp, vp, i32, u64, pu64, pu64, u32, C.POINTER(vp), pu64]
     L.shk_upload_text.argtypes = [vp, vp, u64, C.POINTER(vp)]
     L.shk_count_words.argtypes = [vp, vp, u64, u32, C.POINTER(BatchStats)]
@@ -245,6 +255,18 @@ class Context:
         self._chk(self.L.shk_count_chunks(self.h, ptr, 1 if on_device else 0, n, self._tab(chunk_off),
                                           self._tab(chunk_len), len(chunk_off), C.byref(st)))
         return st.as_dict()
+
+    def count_fasta(self, text, first=True, on_device=False, text_bytes=None):
+        """one piece of a FASTA stream (shk_count_fasta); text: bytes, or an integer pointer with text_bytes given.
+        Returns (batch statistics, FASTA statistics) as dicts."""
+        st, fs = BatchStats(), FastaStats()
+        if on_device or isinstance(text, int):
+            ptr, n = C.c_void_p(int(text)), int(text_bytes)
+        else:
+            buf = (C.c_char * max(len(text), 1)).from_buffer_copy(bytes(text) or b"\0")
+            ptr, n = C.cast(buf, C.c_void_p), len(text)
+        self._chk(self.L.shk_count_fasta(self.h, ptr, 1 if on_device else 0, n, 1 if first else 0, C.byref(st), C.byref(fs)))
+        return st.as_dict(), fs.as_dict()
 
     def upload_text(self, host_ptr, nbytes):
         """start the copy of host text for a later count_chunks(..., on_device=True); returns the device pointer"""
@@ -558,8 +580,8 @@ class Context:
         self._chk(self.L.shk_profile_reset(self.h))
 
     def profile_get(self):
-        arr = (KernelTime * 32)()
-        n = self.L.shk_profile_get(self.h, arr, 32)
+        arr = (KernelTime * 64)()
+        n = self.L.shk_profile_get(self.h, arr, 64)
         return {arr[i].name.decode(): (arr[i].launches, arr[i].ms) for i in range(n) if arr[i].launches}
 
     def last_error_bits(self):
