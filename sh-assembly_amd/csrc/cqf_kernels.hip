@@ -231,6 +231,10 @@ __device__ __forceinline__ void shk_store_image(const ShkMergeArgs &A, uint32_t 
   }
 }
 
+// home entry of a tag (local quotient << 8 | remainder) in the rebuild kernel's LDS hash: 16-bit multiplicative hash,
+// full-rate multiply; 128 tags share an entry
+__device__ __forceinline__ uint32_t shk_fold_home(uint32_t tag) { return (__umul24(tag, 40503u) & 0xFFFFu) >> (16 - SHK_HCAP_LOG2); }
+
 // MODE 0: summary (lengths + statistics). MODE 3: summary that also spills the run lengths and
 // encodings for k_region_place. MODE 1: write pass (free pointers come from k_region_scan_*) for
 // the regions whose runs did not fit the spill record.
@@ -277,7 +281,7 @@ __global__ void __launch_bounds__(SHK_MERGE_GROUP) k_region_merge(ShkMergeArgs A
   __shared__ uint64_t orunw[IMG_BLOCKS];
   __shared__ uint32_t oorank[SHK_REGION_BLOCKS + 1];
   __shared__ uint32_t orrank[IMG_BLOCKS + 1];
-  __shared__ uint32_t s_fail, s_added, s_nlist;
+  __shared__ uint32_t s_fail, s_added;
   // one private word (pair) per lane: where the branch-free probe loop sends the lanes that have nothing to do, so that
   // their no-op atomics do not land on random banks next to the real ones (LDS bank conflicts were 18 % of this kernel's
   // cycles). The words live in `orend`, which is idle until the fold is over -- 512 bytes more would push the plain
@@ -303,8 +307,8 @@ __global__ void __launch_bounds__(SHK_MERGE_GROUP) k_region_merge(ShkMergeArgs A
   const uint32_t ohi = old_any ? (uint32_t)((fa1 - q0) > 0xFFFFFFF ? 0xFFFFFFF : (fa1 - q0)) : olo;
   uint32_t nblk_old = old_any ? (ohi + 63) / 64 : 0;
   if (nblk_old < nown) nblk_old = nown;
-  if (tid == 0) { s_fail = 0; s_added = 0; s_nlist = 0; s_added_b = 0; }
-  // hash slots in use, in order of first insertion (lives in `stage`, which is idle until the merge pass)
+  if (tid == 0) { s_fail = 0; s_added = 0; s_added_b = 0; }
+  // hash slots in use, listed once the fold is over (lives in `stage`, which is idle until the merge pass)
   uint16_t *slist = reinterpret_cast<uint16_t *>(stage);
   bool fatal = false;
   if (!OLDREC && (nblk_old > IMG_BLOCKS || ohi > IMG_SLOTS)) {
@@ -367,9 +371,13 @@ __global__ void __launch_bounds__(SHK_MERGE_GROUP) k_region_merge(ShkMergeArgs A
   SHK_STAMP(0);   // staging + init
   // ---- fold this region's new keys into the LDS hash
   // The kernel is bound by scalar-ALU issue (divergent branches cost s_*exec instructions for the whole
-  // wave), so the probe loop is written branch-free: every lane executes every LDS operation, with
+  // wave), so the probe loops are written branch-free: every lane executes every LDS operation, with
   // operands that make it a no-op for lanes that have nothing (more) to insert -- a compare value no
-  // slot can hold, min with ~0, add 0. Four words per lane probe together; the loop condition is wave-uniform.
+  // slot can hold, min with ~0, add 0. A lane takes four words per round. Each word probes its home entry
+  // first, side by side with the same word of the other lanes: at ~120 keys in 512 entries four words in five
+  // are done then. The words that met a foreign key wait in a queue of the lane's own and are served ONE per
+  // lane and step, so that a step's three LDS atomics carry a collided word of every lane that has one left,
+  // not the few lanes whose word `u` happens to be the collided one. Loop conditions are wave-uniform.
   uint32_t my_added = 0, my_added_b = 0;
   if (A.words && !fatal && !(A.ablate & 1)) {
     const uint64_t kb = A.region_cap ? (uint64_t)r * A.region_cap : A.region_base[r], ke = A.region_cap ? A.region_base[r] : A.region_base[r + 1];
@@ -379,6 +387,25 @@ __global__ void __launch_bounds__(SHK_MERGE_GROUP) k_region_merge(ShkMergeArgs A
     const uint32_t nw = (uint32_t)(ke - kb);   // a region's share of one batch is far below 2^32 words
     if (FUSED && ((ke - kb) >= 32768 || A.counted) && tid == 0) atomicOr(A.err, SHK_E_FUSED);   // (16-bit counters, bit 31 of a word = the "new key" flag)
     const uint32_t *wp = A.words + kb;
+    // a word in flight: tag << SHK_CHUNK_BITS | chunk as the record has them, bit 31 = still to be counted
+    static_assert(16 + SHK_CHUNK_BITS < 31, "a record's tag and chunk leave bit 31 free");
+    constexpr uint32_t QPEND = 0x80000000u, QTAG = 0xFFFFu << SHK_CHUNK_BITS;
+    // One probe of entry `hh` by the lanes whose word `qw` is pending: a CAS / Min / Add group. True where the entry
+    // is the key's (claimed now or earlier) and the word has been counted.
+    auto probe = [&](uint32_t qw, uint32_t hh) -> bool {
+      const bool p = (qw & QPEND) != 0;
+      const uint32_t want = qw & QTAG, chk = qw & (SHK_MAX_CHUNKS - 1);
+      const uint32_t wgt = A.counted ? chk + 1u : 1u;
+      const bool bef = FUSED && chk <= A.split;
+      // the CAS both claims an empty slot and tells what the slot holds otherwise (no separate read);
+      // 0xFFFFFFFE is never stored (tags use 28 bits, SHK_EMPTY is ~0): that compare cannot succeed
+      const uint32_t prev = atomicCAS(p ? &hkey[hh] : &hidle[lane], p ? SHK_EMPTY : 0xFFFFFFFEu, want | (SHK_MAX_CHUNKS - 1));
+      const uint32_t now = (p && prev == SHK_EMPTY) ? want : prev;
+      const bool match = p && (now >> SHK_CHUNK_BITS) == (want >> SHK_CHUNK_BITS);
+      if (wh) atomicMin(match ? &hkey[hh] : &hidle[lane], match ? (want | chk) : 0xFFFFFFFFu);   // first chunk of the key
+      atomicAdd(match ? &hcnt[hh] : &hidle[lane], match ? ((FUSED && !bef) ? wgt << 16 : wgt) : 0u);
+      return match;
+    };
     for (uint32_t i0 = 0; i0 < nw; i0 += 4 * ngrp) {
       uint32_t wv[4];
 #pragma unroll
@@ -386,8 +413,7 @@ __global__ void __launch_bounds__(SHK_MERGE_GROUP) k_region_merge(ShkMergeArgs A
         const uint32_t i = i0 + (uint32_t)u * ngrp + tid;
         wv[u] = i < nw ? wp[i] : ~0u;
       }
-      uint32_t h[4], want[4], chk[4], wgt[4];
-      bool pend[4], bef[4];
+      uint32_t q[4], qh[4];   // the lane's words (QPEND = to be counted) and the entry each probes next
 #pragma unroll
       for (int u = 0; u < 4; u++) {
         // record = (quotient in region << 8 | remainder) << SHK_CHUNK_BITS | chunk (k_rp_scatter, last level)
@@ -397,42 +423,59 @@ __global__ void __launch_bounds__(SHK_MERGE_GROUP) k_region_merge(ShkMergeArgs A
         const uint32_t tag = (w >> SHK_CHUNK_BITS) & 0xFFFFu;
         const bool inr = in && (A.counted || (chunk >= A.chunk_lo && chunk <= A.chunk_hi));
         corrupt |= inr && (tag >> 8) >= nq;
-        pend[u] = inr && (tag >> 8) < nq;
-        want[u] = tag << SHK_CHUNK_BITS;
-        chk[u] = chunk;
-        wgt[u] = A.counted ? chunk + 1u : 1u;
-        bef[u] = FUSED && chunk <= A.split;
-        h[u] = (__umul24(tag, 40503u) & 0xFFFFu) >> (16 - SHK_HCAP_LOG2);   // 16-bit multiplicative hash, full-rate multiply
-        my_added += (pend[u] && !bef[u]) ? wgt[u] : 0u;
-        if (FUSED) my_added_b += (pend[u] && bef[u]) ? wgt[u] : 0u;
+        const bool pend = inr && (tag >> 8) < nq;
+        const uint32_t wgt = A.counted ? chunk + 1u : 1u;
+        const bool bef = FUSED && chunk <= A.split;
+        q[u] = (w & (QTAG | (SHK_MAX_CHUNKS - 1))) | (pend ? QPEND : 0u);
+        qh[u] = shk_fold_home(tag);
+        my_added += (pend && !bef) ? wgt : 0u;
+        if (FUSED) my_added_b += (pend && bef) ? wgt : 0u;
       }
       if (A.ablate & 256) continue;   // diagnostics: loads + setup only
-      uint32_t guard = 0;
-      while (__ballot(pend[0] || pend[1] || pend[2] || pend[3])) {
+      // first probe: word `u` of every lane at its home entry
 #pragma unroll
-        for (int u = 0; u < 4; u++) {
-          if (!__ballot(pend[u])) continue;   // wave-uniform
-          // the CAS both claims an empty slot and tells what the slot holds otherwise (no separate read);
-          // 0xFFFFFFFE is never stored (tags use 28 bits, SHK_EMPTY is ~0): that compare cannot succeed
-          const uint32_t prev = atomicCAS(pend[u] ? &hkey[h[u]] : &hidle[lane], pend[u] ? SHK_EMPTY : 0xFFFFFFFEu, want[u] | (SHK_MAX_CHUNKS - 1));
-          const bool ins = pend[u] && prev == SHK_EMPTY;
-          const uint32_t now = ins ? want[u] : prev;
-          const bool match = pend[u] && (now >> SHK_CHUNK_BITS) == (want[u] >> SHK_CHUNK_BITS);
-          const unsigned long long mi = __ballot(ins);
-          if (mi) {   // wave-uniform: first occurrences append their slot to the list
-            const unsigned first = (unsigned)(__ffsll((long long)mi) - 1);
-            uint32_t base = 0;
-            if (lane == first) base = atomicAdd(&s_nlist, (uint32_t)__popcll(mi));
-            base = (uint32_t)__builtin_amdgcn_readlane((int)base, (int)first);   // (first is wave-uniform: no LDS crossbar)
-            if (ins) slist[base + (uint32_t)__popcll(mi & ((1ULL << lane) - 1))] = (uint16_t)h[u];
-          }
-          if (wh) atomicMin(match ? &hkey[h[u]] : &hidle[lane], match ? (want[u] | chk[u]) : 0xFFFFFFFFu);   // first chunk of the key
-          atomicAdd(match ? &hcnt[h[u]] : &hidle[lane], match ? ((FUSED && !bef[u]) ? wgt[u] << 16 : wgt[u]) : 0u);
-          pend[u] = pend[u] && !match;
-          h[u] = pend[u] ? ((h[u] + 1) & (SHK_HCAP - 1)) : h[u];
+      for (int u = 0; u < 4; u++) {
+        if (!__ballot(q[u] & QPEND)) continue;   // wave-uniform (the last round of a region)
+        const bool match = probe(q[u], qh[u]);
+        q[u] = match ? 0u : q[u];
+        qh[u] = (qh[u] + 1) & (SHK_HCAP - 1);
+      }
+      if (A.ablate & 512) continue;   // diagnostics: the first probe only
+      if (!__ballot((q[0] | q[1] | q[2] | q[3]) & QPEND)) continue;
+      // the words still pending move to the front of the lane's queue (their order is of no account): each pass takes
+      // the first free place to the end
+#pragma unroll
+      for (int pass = 0; pass < 3; pass++) {
+#pragma unroll
+        for (int u = 0; u < 3 - pass; u++) {
+          const bool hole = !(q[u] & QPEND);
+          qh[u] = hole ? qh[u + 1] : qh[u];
+          const uint32_t up = hole ? 0u : q[u + 1];
+          q[u] = hole ? q[u + 1] : q[u];
+          q[u + 1] = up;
         }
-        if (A.ablate & 512) break;      // diagnostics: one probe step only
-        if (++guard > SHK_HCAP) { hfull = pend[0] || pend[1] || pend[2] || pend[3]; break; }
+      }
+      // one word per lane and step: the head of the queue probes its next entry; counted (or dropped, table full) it
+      // leaves and the queue moves up. A word has gone round the table when its next entry is its home again; that
+      // takes SHK_HCAP - 1 steps at the least, so the test sits behind a wave-uniform count of the steps.
+      uint32_t steps = 0;
+      while (__ballot(q[0] & QPEND)) {
+        const bool p = (q[0] & QPEND) != 0;
+        const bool match = probe(q[0], qh[0]);
+        const uint32_t nh = (qh[0] + 1) & (SHK_HCAP - 1);
+        bool keep = p && !match;
+        if (++steps >= SHK_HCAP - 1) {
+          const bool full = keep && nh == shk_fold_home((q[0] & QTAG) >> SHK_CHUNK_BITS);
+          hfull |= full;
+          keep = keep && !full;
+        }
+        qh[0] = keep ? nh : qh[1];
+        q[0] = keep ? q[0] : q[1];
+        qh[1] = keep ? qh[1] : qh[2];
+        q[1] = keep ? q[1] : q[2];
+        qh[2] = keep ? qh[2] : qh[3];
+        q[2] = keep ? q[2] : q[3];
+        q[3] = keep ? q[3] : 0u;
       }
     }
     if (__ballot(corrupt) && corrupt) atomicOr(A.err, SHK_E_CORRUPT);
@@ -496,7 +539,31 @@ __global__ void __launch_bounds__(SHK_MERGE_GROUP) k_region_merge(ShkMergeArgs A
   my_added_b = (FUSED && tid == 0) ? s_added_b : 0;
   SHK_STAMP(2);   // old structure (rank/select) when this wave did it
   // ---- group the new entries by quotient (counting sort of hash slots), sort by remainder
-  const uint32_t nlist = (A.ablate & 16) ? 0 : s_nlist;
+  // The entries the fold has claimed, eight consecutive ones per lane: their order is of no account (grouped by quotient
+  // and sorted by remainder below). Listing them here, once, costs the first wave two 16-byte reads, a wave sum and its
+  // stores; an append at every first occurrence cost both waves a ballot, a returning atomic and a store at every probe.
+  uint32_t nlist;
+  {
+    constexpr uint32_t EPL = SHK_HCAP / nthr;   // entries per lane
+    static_assert(EPL % 4 == 0 && EPL <= 32, "whole 16-byte reads; a lane's entries in one mask");
+    uint32_t used = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < EPL; j += 4) {
+      const uint4 k4 = reinterpret_cast<const uint4 *>(hkey)[(tid * EPL + j) / 4];
+      used |= (uint32_t)(k4.x != SHK_EMPTY) << j | (uint32_t)(k4.y != SHK_EMPTY) << (j + 1) | (uint32_t)(k4.z != SHK_EMPTY) << (j + 2) | (uint32_t)(k4.w != SHK_EMPTY) << (j + 3);
+    }
+    const uint32_t mine = (uint32_t)__popc(used);
+    const uint32_t incl = shk_wave_incl_add(mine);
+    uint32_t pos = incl - mine;
+#pragma unroll
+    for (uint32_t j = 0; j < EPL; j++) {
+      if ((used >> j) & 1u) slist[pos] = (uint16_t)(tid * EPL + j);
+      pos += (used >> j) & 1u;
+    }
+    nlist = (uint32_t)__builtin_amdgcn_readlane((int)incl, SHK_WAVE - 1);
+    if (A.ablate & 16) nlist = 0;
+  }
+  shk_wave_sync();
   for (uint32_t i = tid; i < nlist; i += nthr) { const uint32_t q = hkey[slist[i]] >> (SHK_CHUNK_BITS + 8); atomicAdd(&qcntw[q >> 1], 1u << (16 * (q & 1))); }
   shk_wave_sync();
   constexpr uint32_t per = SHK_REGION / nthr;  // consecutive quotients per lane
