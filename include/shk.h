@@ -478,6 +478,10 @@ int shk_profile_reset(shk_ctx *ctx);
 const char *shk_strerror(int code);
 /* last kernel error bits (diagnostics) */
 uint32_t shk_last_error_bits(shk_ctx *ctx);
+/* diagnostics: batches since shk_create whose key words left the first partition level as split records (4 + 1 bytes per
+ * key instead of 8, between the roll kernels and the middle level of a three-level context that owns the whole filter;
+ * SHK_RP_SPLIT=0, read by shk_create, keeps every batch on 8-byte words). The profile's kernel names do not tell. */
+uint64_t shk_split_batches(shk_ctx *ctx);
 
 #ifdef __cplusplus
 }

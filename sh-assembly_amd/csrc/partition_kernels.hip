@@ -34,6 +34,8 @@ struct ShkRpLevel {
                       // reserve from the same P addresses. Measured on 832 M keys: the scatter itself is unchanged (its
                       // first level stays at 4.7 ms against 3.2 for the second: not the atomics), the hash kernel's
                       // histogram flush gets 5 % off that kernel
+  uint32_t kb;        // RP_SPLIT_IN only: key bits of the split record (below)
+  uint64_t hi_off;    // RP_SPLIT_IN only: bytes from the input's 4-byte plane to its byte plane = 4 * (positions of the input's extent)
 };
 
 __device__ __forceinline__ uint32_t shk_word_region(uint64_t w, uint32_t hb, uint64_t q_lo) {
@@ -46,12 +48,29 @@ __device__ __forceinline__ uint32_t shk_word_region(uint64_t w, uint32_t hb, uin
 //   rec32 = ((last digit << 16 | quotient in region << 8 | remainder) << cb) | chunk
 // is all that anybody still reads of it: half the bytes of the key word. (The digit and the quotient in the region are
 // adjacent bits of the quotient: the upper field is the low 16 + b_last bits of key - (q_lo << 8).)
-enum { RP_WORDS = 0, RP_NARROW_OUT = 1, RP_NARROW_IN = 2 };   // k_rp_scatter: 8-byte words in and out (the last level: 4-byte
-                                                              // records out); writes the narrow record; reads it
+enum { RP_WORDS = 0, RP_NARROW_OUT = 1, RP_NARROW_IN = 2, RP_SPLIT_IN = 3 };   // k_rp_scatter: 8-byte words in and out (the last
+                                                              // level: 4-byte records out); writes the narrow record; reads it;
+                                                              // reads the split record and writes the narrow one
 __device__ __forceinline__ uint32_t shk_narrow_rec(uint64_t w, uint32_t hb, uint64_t q_lo, uint32_t cb) {
   const uint64_t key = hb >= 64 ? w : (w & ((1ULL << hb) - 1));
   const uint32_t up = (uint32_t)(key - (q_lo << 8)) & ((1u << (32 - cb)) - 1);
   return (up << cb) | ((uint32_t)(w >> hb) & ((1u << cb) - 1));
+}
+
+// The split record: what k_roll_scatter hands to the middle level of a three-level context that owns the whole filter, for
+// the batches that are narrow. Behind the first level a word's bucket is its first digit, so all that is still read of it
+// are the kb = rbits + 16 - bits0 bits of key - (q_lo << 8) below that digit and the chunk tag (< 2^cb, cb as above):
+//   rec40 = chunk << kb | ((key - (q_lo << 8)) & (2^kb - 1)),      kb + cb <= 40 and kb <= 32 (create_init)
+// kept as two planes in the buffer the 8-byte words would use: lo32 = its low 32 bits at positions [0, E) of a uint32_t
+// array, hi8 = rec40 >> 32 at byte 4 * E + position, E = the extent in positions the 8-byte form has (all slots of a
+// slotted batch, the buffer's capacity otherwise): 5 bytes per key written and read instead of 8. With kb <= 32 the high
+// byte holds bits of the chunk only, so it is one value per read for the kernel that writes it. The middle level
+// (RP_SPLIT_IN) takes its digit from the key bits and builds the narrow record from the two planes, bit for bit
+// shk_narrow_rec's; a key masked to hb bits cannot lie outside a context that owns the whole filter, so that form has no
+// SHK_E_CORRUPT check.
+__device__ __forceinline__ uint32_t shk_split_to_narrow(uint32_t lo32, uint32_t hi8, uint32_t kb, uint32_t cb) {
+  const uint32_t chunk = (uint32_t)((((uint64_t)hi8 << 32) | lo32) >> kb) & ((1u << cb) - 1);
+  return ((lo32 & ((1u << (32 - cb)) - 1)) << cb) | chunk;
 }
 
 // ---------------------------------------------------------------- exclusive scan (3 kernels)
@@ -247,7 +266,8 @@ __global__ void k_rp_slot_bases(uint64_t *base, uint64_t *cursor, uint64_t n, ui
 
 // FORM (RP_WORDS, RP_NARROW_OUT, RP_NARROW_IN): which of `in` and `out` holds narrow records. A narrow record is made
 // from the key word as it is loaded (the last place the whole key exists: the SHK_E_CORRUPT check of a narrow batch is
-// here), so that the registers and the LDS stage of those instantiations hold 4 bytes per key.
+// here), so that the registers and the LDS stage of those instantiations hold 4 bytes per key. RP_SPLIT_IN is RP_NARROW_OUT
+// behind another load: the split record's two planes (lv.kb, lv.hi_off) instead of the 8-byte word.
 template <int TILE_LOG2, int THREADS, int PMAX = SHK_RP_MAXP, int FORM = RP_WORDS>
 __global__ void __launch_bounds__(THREADS) k_rp_scatter(const uint64_t *in_, uint64_t *out, const uint64_t *n_p,
                                                         const uint64_t *bucket_base, const uint64_t *bucket_end, const uint32_t *tfb,
@@ -255,7 +275,8 @@ __global__ void __launch_bounds__(THREADS) k_rp_scatter(const uint64_t *in_, uin
   constexpr uint32_t SHK_RP_TILE_ = 1u << TILE_LOG2;
   constexpr int KPT_ = (int)(SHK_RP_TILE_ / THREADS);   // keys per thread (registers)
   static_assert(SHK_RP_TILE_ <= 65536, "a rank inside a digit takes 16 bits");
-  using WIN = typename std::conditional<FORM == RP_NARROW_IN, uint32_t, uint64_t>::type;    // what is loaded
+  using WIN = typename std::conditional<FORM == RP_NARROW_IN || FORM == RP_SPLIT_IN, uint32_t, uint64_t>::type;    // what is loaded
+  constexpr bool NOUT = FORM == RP_NARROW_OUT || FORM == RP_SPLIT_IN;                         // narrow records leave
   using WST = typename std::conditional<FORM == RP_WORDS, uint64_t, uint32_t>::type;        // what is held and staged
   const WIN *in = reinterpret_cast<const WIN *>(in_);
   __shared__ uint32_t lh[PMAX];      // digit counts (= next rank while counting); PMAX >= 2^lv.bits (the host's choice)
@@ -277,10 +298,12 @@ __global__ void __launch_bounds__(THREADS) k_rp_scatter(const uint64_t *in_, uin
     const uint32_t cnt = (uint32_t)(hi - lo);
     for (uint32_t d = threadIdx.x; d < P; d += THREADS) lh[d] = 0;
     WIN w[KPT_];
+    uint32_t h8[KPT_];               // RP_SPLIT_IN: the byte plane
 #pragma unroll
     for (int u = 0; u < KPT_; u++) {
       const uint32_t i = threadIdx.x + (uint32_t)u * THREADS;
       w[u] = i < cnt ? in[lo + i] : 0;
+      if (FORM == RP_SPLIT_IN) h8[u] = i < cnt ? reinterpret_cast<const uint8_t *>(in_)[lv.hi_off + lo + i] : 0;
     }
     __syncthreads();
     uint32_t dr[KPT_];               // digit << 16 | rank inside the digit (rank < SHK_RP_TILE)
@@ -293,7 +316,11 @@ __global__ void __launch_bounds__(THREADS) k_rp_scatter(const uint64_t *in_, uin
       if (i < cnt) {
         uint32_t d;
         if (FORM == RP_NARROW_IN) d = (uint32_t)(w[u] >> (16 + lv.cb));
-        else d = (shk_word_region(w[u], lv.hb, lv.q_lo) >> lv.shift) & (P - 1);
+        else if (FORM == RP_SPLIT_IN) {
+          // (the digit's top bit is bit kb - 1 of the record: no chunk bit gets into it)
+          d = ((uint32_t)w[u] >> (16 + lv.shift)) & (P - 1);
+          x[u] = (WST)shk_split_to_narrow((uint32_t)w[u], h8[u], lv.kb, lv.cb);
+        } else d = (shk_word_region(w[u], lv.hb, lv.q_lo) >> lv.shift) & (P - 1);
         if (FORM == RP_NARROW_OUT) {
           const uint64_t key = lv.hb >= 64 ? w[u] : (w[u] & ((1ULL << lv.hb) - 1));
           if ((key >> 8) - lv.q_lo >= lv.nslots) atomicOr(err, SHK_E_CORRUPT);
@@ -327,7 +354,7 @@ __global__ void __launch_bounds__(THREADS) k_rp_scatter(const uint64_t *in_, uin
       if (i < cnt) stage[lbase[dr[u] >> 16] + (dr[u] & 0xFFFFu)] = x[u];
     }
     __syncthreads();
-    if (FORM == RP_NARROW_OUT) {
+    if (NOUT) {
       // the staged record no longer holds this level's digit: a wave takes whole digit runs (lh[] still holds their lengths).
       // This trades balance for not keeping the digit: a run that is no multiple of 64 records leaves lanes idle (hash
       // values: 128 runs of ~128 records over 16 waves here), and a batch whose keys crowd into one digit is written by one

@@ -23,6 +23,7 @@
 // and the first window of a (sub)read is the same recurrence from fh = rh = 0 with the `out` terms left away
 // (k steps: fh = XOR rol(seed[c_j], k-1-j), rh = XOR rol(seedc[c_j], j), nthash.hpp:295-302).
 #include "shk_device.h"
+#include <type_traits>
 
 #define SHK_ROLL_STEPS 16          // bases per round and thread = one 16-byte load per stream
 
@@ -45,6 +46,9 @@ struct ShkRollArgs {
   const struct ShkQuad *pk;
   const uint64_t *pk_base;
   const uint32_t *pk_flag;
+  // k_roll_scatter's split form only (partition_kernels.hip: the split record): key bits kept behind the first digit;
+  // `out` then holds `cap` 4-byte words with `cap` bytes behind them
+  uint32_t kb;
 };
 
 // The two tables in LDS, indexed by the raw BYTE (no code lookup in between): row c of `in` = {seed[c], rol(seedc[c], k-1)},
@@ -390,14 +394,24 @@ __global__ void k_roll_fold(const uint64_t *hist2, uint32_t p0, uint32_t p1, uin
   hist0[d] = t;
 }
 
+// The LDS stage of k_roll_scatter: 8-byte key words, or the two planes of the split record
+template <uint32_t TILE, bool SPLIT> struct ShkRollStage { uint64_t w[TILE]; };
+template <uint32_t TILE> struct ShkRollStage<TILE, true> { uint32_t w[TILE]; uint8_t hi[TILE]; };
+
 // pass 2: the keys again, straight into their buckets. THREADS x 16 keys per window.
-template <int THREADS, int NQ>
+// SPLIT: the split record instead of the 8-byte word (partition_kernels.hip, next to shk_narrow_rec): a lane's sixteen
+// waiting keys are sixteen 32-bit registers, their first digits (which the record does not hold) wait two to a register, and
+// the high byte -- bits of the chunk tag only -- is one value per read. The stage is a 4-byte and a 1-byte array (80 KB
+// instead of 128), and since a staged record cannot say where it goes, a wave drains whole digit runs, as k_rp_scatter's
+// RP_NARROW_OUT does.
+template <int THREADS, int NQ, bool SPLIT = false>
 __global__ void __launch_bounds__(THREADS) k_roll_scatter(ShkRollArgs A) {
   constexpr uint32_t TILE = THREADS * SHK_ROLL_STEPS;
+  using WK = typename std::conditional<SPLIT, uint32_t, uint64_t>::type;      // a key as it waits in registers
   __shared__ ShkRollTabs T;
   __shared__ uint32_t lh[1024], lbase[1024];
   __shared__ uint64_t gbase[1024];
-  __shared__ uint64_t stage[TILE];
+  __shared__ ShkRollStage<TILE, SPLIT> stage;
   __shared__ uint32_t scratch[SHK_MAX_WAVES + 1];
   __shared__ uint32_t any_left;
   shk_roll_tabs_init(&T, A.k);
@@ -409,6 +423,8 @@ __global__ void __launch_bounds__(THREADS) k_roll_scatter(ShkRollArgs A) {
   ShkRollState s;
   s.st = 0; s.len = 0; s.i = 0; s.fill = 0; s.fh = 0; s.rh = 0;
   uint64_t tag = 0;
+  uint32_t tag_lo = 0, tag_hi = 0; // SPLIT: chunk << kb as the record's two planes see it
+  const uint32_t kmask = A.kb >= 32 ? ~0u : (1u << A.kb) - 1, qlo8 = (uint32_t)(A.q_lo << 8);
   bool have = false;
   for (;;) {
     // a thread whose read is used up takes its next one
@@ -417,7 +433,10 @@ __global__ void __launch_bounds__(THREADS) k_roll_scatter(ShkRollArgs A) {
       if (en - st > 65535) atomicOr(A.err, SHK_E_BAD_FASTQ);                       // SHK_MAX_READ (a slotted batch has no histogram pass to say so)
       if (en - st <= 65535 && en - st >= A.k) {
         s.st = st; s.len = (uint32_t)(en - st); s.i = 0; s.fill = 0; s.fh = 0; s.rh = 0;
-        tag = (uint64_t)(A.chunk_first + A.rd_chunk[r] * A.chunk_mul) << A.hb;
+        if constexpr (SPLIT) {
+          const uint64_t t = (uint64_t)(A.chunk_first + A.rd_chunk[r] * A.chunk_mul) << A.kb;
+          tag_lo = (uint32_t)t; tag_hi = (uint32_t)(t >> 32);
+        } else tag = (uint64_t)(A.chunk_first + A.rd_chunk[r] * A.chunk_mul) << A.hb;
         if (A.pk && !(A.pk_flag[r] >> 31)) s.st = A.pk_base[r] | (1ULL << 63);     // staged: its first unit instead of its text offset
         have = true;
       }
@@ -426,12 +445,17 @@ __global__ void __launch_bounds__(THREADS) k_roll_scatter(ShkRollArgs A) {
     for (uint32_t d = threadIdx.x; d < P; d += THREADS) lh[d] = 0;
     if (threadIdx.x == 0) any_left = 0;
     shk_lds_barrier();             // (the previous window's runs keep draining to HBM while this one is hashed)
-    uint64_t w[SHK_ROLL_STEPS];
+    WK w[SHK_ROLL_STEPS];
+    uint32_t dg[SHK_ROLL_STEPS / 2] = {};            // SPLIT: the keys' first digits (< 2^10), taken while the whole key is in hand
     uint32_t vm = 0;               // steps that completed a k-mer
     if (have) {
       const auto keep = [&](int j, uint64_t key) {
-        w[j] = key | tag;
-        atomicAdd(&lh[shk_roll_digit(key, A)], 1u);
+        const uint32_t d = shk_roll_digit(key, A);
+        if constexpr (SPLIT) {
+          w[j] = (((uint32_t)key - qlo8) & kmask) | tag_lo;
+          dg[j >> 1] |= d << (16 * (j & 1));
+        } else w[j] = key | tag;
+        atomicAdd(&lh[d], 1u);
         vm |= 1u << j;
       };
       have = (s.st >> 63) ? shk_roll_round_pk(&T, A.pk + (s.st & ~(1ULL << 63)), s, A.k, mask, keep)
@@ -457,15 +481,38 @@ __global__ void __launch_bounds__(THREADS) k_roll_scatter(ShkRollArgs A) {
     }
     __syncthreads();
     const uint32_t cnt = carry;
+    if constexpr (SPLIT) {
 #pragma unroll
-    for (int u = 0; u < SHK_ROLL_STEPS; u++)
-      if ((vm >> u) & 1u) stage[atomicAdd(&lbase[shk_roll_digit(A.hb >= 64 ? w[u] : (w[u] & mask), A)], 1u)] = w[u];
-    __syncthreads();
-    for (uint32_t i = threadIdx.x; i < cnt; i += THREADS) {
-      const uint64_t x = stage[i];
-      const uint32_t d = shk_roll_digit(A.hb >= 64 ? x : (x & mask), A);
-      const uint64_t at = gbase[d] + i;
-      if (at < A.cap) A.out[at] = x; else atomicOr(A.err, SHK_E_KEYS_FULL);
+      for (int u = 0; u < SHK_ROLL_STEPS; u++)
+        if ((vm >> u) & 1u) {
+          const uint32_t at = atomicAdd(&lbase[(dg[u >> 1] >> (16 * (u & 1))) & 0xFFFFu], 1u);
+          stage.w[at] = w[u];
+          stage.hi[at] = (uint8_t)tag_hi;
+        }
+      __syncthreads();
+      // run d is [lbase[d] - lh[d], lbase[d]) of the stage now; both planes of it go out under one bound
+      uint32_t *out_lo = reinterpret_cast<uint32_t *>(A.out);
+      uint8_t *out_hi = reinterpret_cast<uint8_t *>(A.out) + 4 * A.cap;
+      for (uint32_t d = threadIdx.x / SHK_WAVE; d < P; d += THREADS / SHK_WAVE) {
+        const uint32_t len = lh[d], l0 = lbase[d] - len;
+        const uint64_t g0 = gbase[d] + l0;
+        for (uint32_t j = threadIdx.x % SHK_WAVE; j < len; j += SHK_WAVE) {
+          const uint64_t at = g0 + j;
+          if (at < A.cap) { out_lo[at] = stage.w[l0 + j]; out_hi[at] = stage.hi[l0 + j]; }
+          else atomicOr(A.err, SHK_E_KEYS_FULL);
+        }
+      }
+    } else {
+#pragma unroll
+      for (int u = 0; u < SHK_ROLL_STEPS; u++)
+        if ((vm >> u) & 1u) stage.w[atomicAdd(&lbase[shk_roll_digit(A.hb >= 64 ? w[u] : (w[u] & mask), A)], 1u)] = w[u];
+      __syncthreads();
+      for (uint32_t i = threadIdx.x; i < cnt; i += THREADS) {
+        const uint64_t x = stage.w[i];
+        const uint32_t d = shk_roll_digit(A.hb >= 64 ? x : (x & mask), A);
+        const uint64_t at = gbase[d] + i;
+        if (at < A.cap) A.out[at] = x; else atomicOr(A.err, SHK_E_KEYS_FULL);
+      }
     }
     shk_lds_barrier();
     if (!more) break;

@@ -130,6 +130,8 @@ struct ShkStageBufs {
   int slots_off = 0;
   uint64_t roll_cap = 0;        // the batch in hand: 0 = roll_stage left exact bucket bases; else digit d owns the slot [d * roll_cap, ...)
                                 // of d_words[0] and d_end[1][d] is its end (k_roll_slot_ends)
+  bool roll_split = false;      // the batch in hand: d_words[0] holds the split record's two planes (roll_keys), not 8-byte words
+  uint64_t split_batches = 0;   // batches that took that form (shk_split_batches)
   uint32_t up_overflows = 0;    // consecutive batches whose slotted upper levels overflowed (SHK_E_SLOT_FULL_UP); at 2 they are
   int up_off = 0;               // switched off. Apart from slot_overflows, which counts the last level's
   // profiling
@@ -151,6 +153,8 @@ struct shk_ctx : ShkStageBufs {
   ShkPartLevel part[4];         // the partition plan, level by level
   bool roll_two;                // roll_stage's histogram pass counts the first two levels' digits together (they fit its LDS bins)
   bool roll_slots;              // three levels, all slotted: a narrow batch of text runs without any counting pass (roll_stage)
+  uint32_t split_kb;            // 0 = off, else the key bits of the split record between the roll kernels and the middle level
+                                // (partition_kernels.hip): three levels, the middle one may be narrow, the whole filter is this context's
   bool parse_mask;              // k_count_lines keeps the newline flags and k_emit_reads reads them, not the text (parse_stage)
   uint32_t threads, hash_groups;
   // state
@@ -383,6 +387,7 @@ static int create_init(shk_ctx *c, const shk_config *cfg) {
       left -= bits;
       c->lv[l].shift = left; c->lv[l].bits = bits; c->lv[l].nbuckets = nb; c->lv[l].hb = cfg->hb; c->lv[l].q_lo = c->q_lo;
       c->lv[l].nslots = c->nslots; c->lv[l].cb = 0; c->lv[l].out32 = 0; c->lv[l].ablate = 0; c->lv[l].ng_log2 = 0; c->lv[l].slot_cap = 0;
+      c->lv[l].kb = 0; c->lv[l].hi_off = 0;
       nb <<= bits;
     }
     c->lv[c->nlevels - 1].out32 = 1;
@@ -413,6 +418,15 @@ static int create_init(shk_ctx *c, const shk_config *cfg) {
   c->roll_slots = c->nlevels == 3 && c->part[1].may_narrow && c->part[2].may_slot &&
                   !(getenv("SHK_ROLL_SLOTS") && atoi(getenv("SHK_ROLL_SLOTS")) == 0) &&
                   cfg->max_batch_keys / (level_out(c, 1)) >= 28800;
+  // The split record between k_roll_scatter and the middle level: three levels with a narrow middle one (so SHK_RP_WORDS8=1
+  // implies off), the whole filter here (a key masked to hb bits is then in range, which is what lets the middle level drop
+  // its SHK_E_CORRUPT check), and the record's fields fit 40 bits. kb <= 32 (the high byte holds chunk bits only) follows
+  // from the levels' even split: kb + cb <= 40 means rbits <= 25, and then kb <= 32. SHK_RP_SPLIT=0: every batch on 8-byte words
+  c->split_kb = 0;
+  if (c->nlevels == 3 && c->part[1].may_narrow && ns == 1 && !(getenv("SHK_RP_SPLIT") && atoi(getenv("SHK_RP_SPLIT")) == 0)) {
+    const uint32_t kb = c->rbits + 16 - c->lv[0].bits;
+    if (kb + c->lv[1].cb <= 40 && kb <= 32) c->split_kb = kb;
+  }
   // SHK_PARSE_MASK=0: k_emit_reads reads the text again
   c->parse_mask = !(getenv("SHK_PARSE_MASK") && atoi(getenv("SHK_PARSE_MASK")) == 0);
   c->fasta_seg = SHK_FASTA_SEGMENT;
@@ -663,7 +677,7 @@ static void roll_args(const shk_ctx *c, ShkStageBufs *b, ShkRollArgs &A, const u
   A.text = dtext; A.safe_end = (text_bytes + 15) & ~15ULL;
   A.rd_start = b->d_rd_start; A.rd_end = b->d_rd_end; A.nreads_p = b->d_scalars + DS_NREADS; A.rd_chunk = b->d_rd_chunk;
   A.chunk_first = chunk_first; A.chunk_mul = chunk_mul; A.k = c->cfg.k; A.hb = c->cfg.hb;
-  A.cap = c->cfg.max_batch_keys; A.err = b->d_err;
+  A.cap = c->cfg.max_batch_keys; A.err = b->d_err; A.kb = 0;
 }
 // wide: A.hist_bits may exceed 10 (up to 14: two levels' digits together)
 static void launch_roll_hist(const shk_ctx *c, ShkStageBufs *b, const ShkRollArgs &A, uint64_t nreads, bool wide) {
@@ -676,14 +690,18 @@ static void launch_roll_hist(const shk_ctx *c, ShkStageBufs *b, const ShkRollArg
   else if (wide) hipLaunchKernelGGL((k_roll_hist<14, 512>), grid, dim3(512), 0, b->stream, A);
   else hipLaunchKernelGGL((k_roll_hist<10, 256>), grid, dim3(256), 0, b->stream, A);
 }
-static void launch_roll_scatter(const shk_ctx *c, ShkStageBufs *b, const ShkRollArgs &A, uint64_t nreads) {
+static void launch_roll_scatter(const shk_ctx *c, ShkStageBufs *b, const ShkRollArgs &A, uint64_t nreads, bool split = false) {
   ProfScope ps(c, b, KP_ROLL_SCATTER);
   if (c->threads >= 512) {
     const uint64_t blocks = nreads / 1024 + 1;
-    hipLaunchKernelGGL((k_roll_scatter<1024, 1>), dim3((uint32_t)(blocks < 512 ? blocks : 512)), dim3(1024), 0, b->stream, A);
+    const dim3 grid((uint32_t)(blocks < 512 ? blocks : 512));
+    if (split) hipLaunchKernelGGL((k_roll_scatter<1024, 1, true>), grid, dim3(1024), 0, b->stream, A);
+    else hipLaunchKernelGGL((k_roll_scatter<1024, 1>), grid, dim3(1024), 0, b->stream, A);
   } else {          // (small workgroups: the CPU emulator build of the tests)
     const uint64_t blocks = nreads / 64 + 1;
-    hipLaunchKernelGGL((k_roll_scatter<64, 4>), dim3((uint32_t)(blocks < 64 ? blocks : 64)), dim3(64), 0, b->stream, A);
+    const dim3 grid((uint32_t)(blocks < 64 ? blocks : 64));
+    if (split) hipLaunchKernelGGL((k_roll_scatter<64, 4, true>), grid, dim3(64), 0, b->stream, A);
+    else hipLaunchKernelGGL((k_roll_scatter<64, 4>), grid, dim3(64), 0, b->stream, A);
   }
 }
 
@@ -706,6 +724,7 @@ static uint64_t up_slot_capacity(double m, uint64_t unit) {
 struct ShkRollBatch {
   const uint8_t *dtext; uint64_t text_bytes, nreads;
   uint32_t nchunks, chunk_first, chunk_mul;
+  bool split;           // the batch may leave the roll kernels as split records (split_batch)
   bool staged;          // every read lies in 2-bit units already (shk_count_fasta): d_words[1], d_key_base and d_nkeys are as pack_stage leaves them
 };
 
@@ -717,7 +736,7 @@ static int roll_keys(const shk_ctx *c, ShkStageBufs *b, const ShkRollBatch &R, b
   // the first two levels' digits together, when they fit the histogram pass's LDS bins
   const uint32_t cb = c->lv[0].bits + c->lv[1].bits;
   const bool two = c->roll_two;
-  b->roll_cap = 0;
+  b->roll_cap = 0; b->roll_split = false;
   if (slots) {
     // the host's only bound on the keys before they are hashed: a base needs a quality byte
     const uint64_t U = c->cfg.max_batch_keys < R.text_bytes / 2 ? c->cfg.max_batch_keys : R.text_bytes / 2;
@@ -737,10 +756,14 @@ static int roll_keys(const shk_ctx *c, ShkStageBufs *b, const ShkRollBatch &R, b
   A.hist = two ? b->d_hist[1] : b->d_hist[0]; A.hist_shift = two ? c->lv[1].shift : c->lv[0].shift; A.hist_bits = two ? cb : c->lv[0].bits;
   A.cursor = b->d_cursor; A.out = b->d_words[0];
   if (cap0) A.cap = P * cap0;
+  // Split records, unless the middle level would have to count them: its counting pass (k_rp_hist) reads 8-byte words. A
+  // slotted batch has no counting pass, and one with counted bases has the middle level's counts from k_roll_hist when the
+  // two levels' digits fit its bins (`two`); where they do not, the batch stays on 8-byte words
+  if (R.split && (cap0 || two)) { b->roll_split = true; b->split_batches++; A.kb = c->split_kb; }
   if (R.staged) { A.pk = (const ShkQuad *)b->d_words[1]; A.pk_base = b->d_key_base; A.pk_flag = b->d_nkeys; }
   else { int rc = pack_stage(c, b, A, R.nreads, R.text_bytes, b->d_words[1]); if (rc) return rc; }     // (d_words[1]: the partition's other buffer, idle until its second level)
   if (cap0) {
-    launch_roll_scatter(c, b, A, R.nreads);
+    launch_roll_scatter(c, b, A, R.nreads, b->roll_split);
     ProfScope ps(c, b, KP_RP_PREP);
     hipLaunchKernelGGL(k_roll_slot_ends, dim3(1), dim3(c->threads < 256 ? c->threads : 256), 0, b->stream, (const uint64_t *)b->d_cursor, (uint32_t)P, cap0,
                        b->d_end[1], b->d_scalars + DS_NWORDS, b->d_err);
@@ -755,11 +778,14 @@ static int roll_keys(const shk_ctx *c, ShkStageBufs *b, const ShkRollBatch &R, b
   if (run_scan<uint64_t>(c, b, b->d_hist[0], P, nullptr, b->d_base[1])) return SHK_ERR_HIP;
   HIPCHK(hipMemcpyAsync(b->d_scalars + DS_NWORDS, b->d_base[1] + P, 8, hipMemcpyDeviceToDevice, b->stream));
   HIPCHK(hipMemcpyAsync(b->d_cursor, b->d_base[1], P * 8, hipMemcpyDeviceToDevice, b->stream));
-  launch_roll_scatter(c, b, A, R.nreads);
+  launch_roll_scatter(c, b, A, R.nreads, b->roll_split);
   HIPCHK(hipGetLastError());
   return SHK_OK;
 }
 
+// May this batch of text leave the roll kernels as split records? The plan allows it and the batch is narrow (the rule
+// partition_stage applies to the middle level).
+static bool split_batch(const shk_ctx *c, uint32_t nchunks) { return c->split_kb && nchunks && nchunks <= (1u << c->lv[1].cb); }
 // Does this batch run without counting passes above the last level? The plan allows it, the batch is narrow (the middle
 // level's slots hold narrow records) and two overflows in a row have not switched the upper slots off.
 static bool roll_slots_batch(const shk_ctx *c, const ShkStageBufs *b, uint32_t nchunks) {
@@ -769,6 +795,7 @@ static int roll_stage(const shk_ctx *c, ShkStageBufs *b, const void *text, int o
                       const uint64_t *chunk_len, uint32_t nchunks, uint32_t chunk_first, uint32_t chunk_mul, ShkRollBatch *R) {
   if (!chunk_labels_ok(nchunks, chunk_first, chunk_mul)) return SHK_ERR_BATCH;
   R->text_bytes = text_bytes; R->nchunks = nchunks; R->chunk_first = chunk_first; R->chunk_mul = chunk_mul;
+  R->split = chunk_first == 0 && chunk_mul == 1 && split_batch(c, nchunks);      // (tags below nchunks)
   { int rc = parse_stage(c, b, text, on_device, text_bytes, chunk_off, chunk_len, nchunks, &R->dtext, &R->nreads); if (rc) return rc; }
   return roll_keys(c, b, *R, roll_slots_batch(c, b, nchunks));
 }
@@ -782,19 +809,22 @@ struct ShkPartInput {
   uint32_t nchunks;      // the words' chunk fields are chunk tags below this; 0: not known (or the field is a multiplicity)
   uint64_t slot_cap0;    // first_level = 1 only, 0 = off: src[0] lies in slots of this many words per first digit, d_end[1] holds the
                          // buckets' ends (ShkStageBufs::roll_cap); the middle level is then slotted too
+  uint64_t split_ext;    // first_level = 1 only, 0 = 8-byte words: src[0] holds split records, 4-byte plane over this many positions and
+                         // the byte plane behind it (ShkStageBufs::roll_split); the batch is narrow then
   bool redo;             // the batch's second time through the partition, after SHK_E_SLOT_FULL_UP: the last level's cursor set-up is
                          // timed with the other preparations, so that k_rp_slot_cursors stays one launch per batch that tried slots
 };
 // roll_stage: d_words[0] sorted by the first digit; the second level is counted when the two levels' digits fit one pass
 static ShkPartInput part_from_roll(const shk_ctx *c, const ShkStageBufs *b, uint64_t n, uint32_t nchunks) {
-  return {{b->d_words[0], nullptr}, {n, 0}, 1, 0, 1, {false, c->roll_two && !b->roll_cap}, nchunks, b->roll_cap, false};
+  return {{b->d_words[0], nullptr}, {n, 0}, 1, 0, 1, {false, c->roll_two && !b->roll_cap}, nchunks, b->roll_cap,
+          b->roll_split ? (b->roll_cap ? b->roll_cap << c->lv[0].bits : c->cfg.max_batch_keys) : 0, false};
 }
 // hash_stage with hist0: d_words[0] in emission order, the first level counted
-static ShkPartInput part_from_hash(const ShkStageBufs *b, uint64_t n, uint32_t nchunks) { return {{b->d_words[0], nullptr}, {n, 0}, 1, 0, 0, {true, false}, nchunks, 0, false}; }
+static ShkPartInput part_from_hash(const ShkStageBufs *b, uint64_t n, uint32_t nchunks) { return {{b->d_words[0], nullptr}, {n, 0}, 1, 0, 0, {true, false}, nchunks, 0, 0, false}; }
 // the caller's words, read in place (no staging copy), in one of the context's own buffers or not. w2: a second source
 // (shk_stage_words_pair: both are counted into one histogram and scattered with one set of cursors)
 static ShkPartInput part_from_words(const ShkStageBufs *b, const uint64_t *w, uint64_t n, const uint64_t *w2 = nullptr, uint64_t n2 = 0) {
-  return {{w, w2}, {n, n2}, w2 ? 2 : 1, w == b->d_words[0] ? 0 : w == b->d_words[1] ? 1 : -1, 0, {false, false}, 0, 0, false};
+  return {{w, w2}, {n, n2}, w2 ? 2 : 1, w == b->d_words[0] ? 0 : w == b->d_words[1] ? 1 : -1, 0, {false, false}, 0, 0, 0, false};
 }
 
 // Last level: fixed-capacity region slots instead of a histogram pass over the keys + scan, when the output buffer
@@ -836,6 +866,8 @@ static int partition_stage(const shk_ctx *c, ShkStageBufs *b, const ShkPartInput
     // 4-byte records between this level and the next: the plan allows it and every chunk tag of the call fits
     const bool narrow_in = narrow;
     narrow = pl.may_narrow && in.nchunks && in.nchunks <= (1u << c->lv[l].cb);
+    const bool split_in = in.split_ext && l == in.first_level;     // this level reads split records
+    if (split_in && !(narrow && l == 1)) return SHK_ERR_CORRUPT;   // (roll_keys splits narrow batches only)
     // the sources of this level: (words, their extent on the device, their bucket bases and ends, their extent on the host)
     struct Src { const uint64_t *w, *n_p, *base, *end; uint64_t n; } srcs[2] = {{l == in.first_level ? in.src[0] : b->d_words[cur], ext_p, b->d_base[l], ends, ext}, {}};
     int nsrc = 1;
@@ -886,6 +918,7 @@ static int partition_stage(const shk_ctx *c, ShkStageBufs *b, const ShkPartInput
                                c->lv[0], c->lv[1], b->d_hist[0], b->d_hist[1], wt);
           counted[1] = true;
         } else if (!counted[l]) {
+          if (split_in) return SHK_ERR_CORRUPT;     // (k_rp_hist reads 8-byte words: roll_keys keeps such a batch on them)
           HIPCHK(hipMemsetAsync(b->d_hist[l], 0, ((nb * P) << c->lv[l].ng_log2) * 8, b->stream));
           ProfScope ps(c, b, KP_RP_HIST);
           const uint32_t wt = nwin / 4096 + 1;   // windows per workgroup
@@ -915,7 +948,15 @@ static int partition_stage(const shk_ctx *c, ShkStageBufs *b, const ShkPartInput
         for (int si = 0; si < nsrc; si++) {
           const Src &S = srcs[si];
           const dim3 wide((uint32_t)(S.n >> SHK_RP_TILE0_LOG2) + 1);
-          if (narrow && pl.scatter == RP_SCATTER_WIDE)
+          if (split_in) {
+            lvl.kb = c->split_kb; lvl.hi_off = 4 * in.split_ext;
+            if (pl.scatter == RP_SCATTER_WIDE)
+              hipLaunchKernelGGL((k_rp_scatter<SHK_RP_TILE0_LOG2, 1024, 256, RP_SPLIT_IN>), wide, dim3(1024), 0, b->stream, S.w, b->d_words[cur ^ 1], S.n_p,
+                                 S.base, S.end, b->d_tfb, lvl, cursor, b->d_err);
+            else
+              hipLaunchKernelGGL((k_rp_scatter<12, SHK_RP_THREADS, SHK_RP_MAXP, RP_SPLIT_IN>), dim3((uint32_t)(S.n / SHK_RP_TILE + 1)), dim3(SHK_RP_THREADS), 0,
+                                 b->stream, S.w, b->d_words[cur ^ 1], S.n_p, S.base, S.end, b->d_tfb, lvl, cursor, b->d_err);
+          } else if (narrow && pl.scatter == RP_SCATTER_WIDE)
             hipLaunchKernelGGL((k_rp_scatter<SHK_RP_TILE0_LOG2, 1024, 256, RP_NARROW_OUT>), wide, dim3(1024), 0, b->stream, S.w, b->d_words[cur ^ 1], S.n_p,
                                S.base, S.end, b->d_tfb, lvl, cursor, b->d_err);
           else if (narrow)
@@ -1939,7 +1980,7 @@ static int fasta_keys(shk_ctx *c, uint64_t nseg, uint64_t nkmers, int *dst) {
   c->h_pinned[HP_NREADS] = nseg;
   HIPCHK(hipMemcpyAsync(c->d_scalars + DS_NREADS, c->h_pinned + HP_NREADS, 8, hipMemcpyHostToDevice, c->stream));
   ShkRollBatch R = {};
-  R.nreads = nseg; R.nchunks = 1; R.chunk_mul = 1; R.staged = true;
+  R.nreads = nseg; R.nchunks = 1; R.chunk_mul = 1; R.staged = true; R.split = split_batch(c, 1);
   if (roll_path(c)) {
     { int rc = roll_keys(c, c, R, false); if (rc) return rc; }
     uint32_t bits = 0;
@@ -2095,7 +2136,7 @@ extern "C" int shk_route_words(shk_ctx *c, uint64_t nwords, uint32_t nshards, ui
   // one partition level over the WHOLE filter's regions: digit = owner
   ShkRpLevel lv;
   lv.shift = (c->cfg.qb - SHK_REGION_LOG2) - lg; lv.bits = lg; lv.nbuckets = 1; lv.hb = c->cfg.hb; lv.q_lo = 0;
-  lv.nslots = ~0ULL; lv.cb = 0; lv.out32 = 0; lv.ablate = 0; lv.ng_log2 = 0; lv.slot_cap = 0;
+  lv.nslots = ~0ULL; lv.cb = 0; lv.out32 = 0; lv.ablate = 0; lv.ng_log2 = 0; lv.slot_cap = 0; lv.kb = 0; lv.hi_off = 0;
   if (set_nwords(c, nwords)) return SHK_ERR_HIP;
   const uint64_t *n_p = c->d_scalars + DS_NWORDS;
   const uint32_t nwin = (uint32_t)(nwords / SHK_RP_TILE + 1);
@@ -3495,6 +3536,8 @@ extern "C" int shk_find_unitigs(shk_ctx *c, const char *seeds, const uint32_t *s
   return rc;
 }
 
+// batches whose first-level output took the split record (either front end), since the context was created
+extern "C" uint64_t shk_split_batches(shk_ctx *c) { return c ? c->split_batches + (c->front ? c->front->b.split_batches : 0) : 0; }
 extern "C" int shk_profile_enable(shk_ctx *c, int on) { if (!c) return SHK_ERR_ARG; c->prof_on = on; return SHK_OK; }
 extern "C" int shk_profile_reset(shk_ctx *c) {
   if (!c) return SHK_ERR_ARG;

@@ -84,7 +84,7 @@ EXPORTS = ["shk_create", "shk_destroy", "shk_count_chunks", "shk_hash_chunks", "
            "shk_stats", "shk_header", "shk_export_blocks", "shk_export_cqf", "shk_import_cqf", "shk_import_blocks",
            "shk_lookup", "shk_profile_enable", "shk_profile_get", "shk_profile_reset", "shk_strerror",
            "shk_last_error_bits", "shk_insert_counted", "shk_dump", "shk_merge", "shk_multi_merge", "shk_import_shards", "shk_table_ptr", "shk_unitigs_add_reads",
-           "shk_spectrum", "shk_inner_product", "shk_magnitude", "shk_intersect", "shk_count_fasta"]
+           "shk_spectrum", "shk_inner_product", "shk_magnitude", "shk_intersect", "shk_count_fasta", "shk_split_batches"]
 
 _libs = {}
 
@@ -150,6 +150,8 @@ def load(path=None):
     L.shk_strerror.restype = C.c_char_p
     L.shk_last_error_bits.argtypes = [vp]
     L.shk_last_error_bits.restype = u32
+    L.shk_split_batches.argtypes = [vp]
+    L.shk_split_batches.restype = u64
     _libs[path] = L
     return L
 
@@ -586,3 +588,7 @@ class Context:
 
     def last_error_bits(self):
         return self.L.shk_last_error_bits(self.h)
+
+    def split_batches(self):
+        """batches since creation whose first-level output took the split record (include/shk.h)"""
+        return int(self.L.shk_split_batches(self.h))

@@ -33,6 +33,11 @@ def main():
         out["kernels"][name] = {"launches": v["launches"], "fetch_bytes_per_launch": int(f / v["launches"]),
                                 "write_bytes_per_launch": int(w / v["launches"])}
         total += f + w
+    # bench.py looks the roll launch up as `k_roll_scatter<1024, 1>`; where every batch of the workload took the split form
+    # (`<1024, 1, true>`) that launch's figures are quoted under the name it looks for as well
+    split, plain = "k_roll_scatter<1024, 1, true>", "k_roll_scatter<1024, 1>"
+    if split in out["kernels"] and plain not in out["kernels"]:
+        out["kernels"][plain] = dict(out["kernels"][split], same_as=split)
     out["bytes_per_step"] = int(total / steps)
     print(json.dumps(out, indent=1))
 
