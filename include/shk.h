@@ -33,6 +33,7 @@
  *   shk_magnitude         qf_magnitude                                      cqf/gqf.c:2760-2763
  *   shk_spectrum          (no counterpart: the reference's README sends the user to an outside program for F0, F1, f1, f2, ...)
  *   shk_count_fasta       (no counterpart: the reference reads 4-line FASTQ only, cqf/CQF_mt.h:610-731) FASTA text of any shape
+ *   shk_sample_chunks     (no counterpart: the reference's README sends the user to ntCard) -N -n -e from the reads themselves
  *   shk_import_shards     (no counterpart: the reference is one process) quotient-range shards -> the single table
  *   shk_stats             runtime->nelts / ndistinct_elts / num_deNoise    cqf/CQF_mt.h:277-288
  *   shk_destroy           CQF_mt::~CQF_mt -> qf_destroy                    cqf/CQF_mt.h:547-557; gqf.c:2306
@@ -203,6 +204,34 @@ int shk_count_words(shk_ctx *ctx, const uint64_t *d_words, uint64_t nwords, uint
 typedef struct shk_fasta_stats { uint64_t records, bases, breaks, kmers; } shk_fasta_stats;
 int shk_count_fasta(shk_ctx *ctx, const void *text, int text_on_device, uint64_t text_bytes, int first,
                     shk_batch_stats *stats, shk_fasta_stats *fstats /* may be NULL */);
+
+/* ---- a hash-sampled spectrum of the reads (no counterpart in the reference, whose README sends the user to ntCard for
+ * the -N -n -e its command line wants). Hashes every k-mer of the FASTQ chunks exactly as shk_count_chunks does (the
+ * reads_to_kmers stream with all its quirks) and KEEPS those whose canonical 64-bit ntHash has bits
+ * [hb, hb + sample_bits) equal to zero; the kept k-mers are counted into the table, exactly, under the key the full filter
+ * would give them (the hash's low hb bits: the sample bits lie directly above the key bits and share none with them).
+ * Whether a k-mer is kept depends on the k-mer alone, so a kept k-mer is kept at every occurrence: the table holds the
+ * exact abundances of a 2^-sample_bits sample of the DISTINCT k-mers, and shk_spectrum of it scaled by 2^sample_bits
+ * estimates F0, f1, f2, ... of the whole input; F1 is counted exactly on the way (sstats->kmers). sample_bits = 0 keeps
+ * everything. (Not the hash's top bits: the canonical hash is the smaller of two, and its leading bits are zero about
+ * twice as often as they should be.)
+ *   - Text and chunks: the contract of shk_count_chunks (host text, or device text that is 16-byte aligned; 1 .. 4096
+ *     chunks in any order, lines counted from each chunk's first byte).
+ *   - To the table the call is ONE chunk: it behaves as shk_count_words on the kept keys with nchunks = 1 (counters,
+ *     `stats`, the deNoise trigger tested once, behind the call). Every geometry.
+ *   - sstats (may be NULL): kmers = every k-mer the text holds (what shk_count_chunks reports as stats->kmers), kept = the
+ *     occurrences kept = stats->kmers of this call.
+ *   - Calls accumulate: sampling with the same sample_bits over any split of the input into calls gives the table of one
+ *     call over all of it. Mixing values of sample_bits in one context is the caller's business; nothing checks it.
+ * Errors leave the table as it was: SHK_ERR_ARG for sample_bits > 24, hb + sample_bits > 56, a sharded context or device
+ * text that is not 16-byte aligned; SHK_ERR_BATCH for more kept words than max_batch_keys, text or reads beyond the
+ * capacities, nchunks outside 1 .. 4096, or batches prepared and not yet counted; SHK_ERR_FASTQ for a read of more than
+ * 65535 bases. (Reads are staged at 2 bits per base where their 64-base units fit max_batch_keys / 2 - 1 and are read
+ * from the text otherwise: the capacity for keys bounds the kept words only.) */
+typedef struct shk_sample_stats { uint64_t kmers, kept; } shk_sample_stats;
+int shk_sample_chunks(shk_ctx *ctx, const void *text, int text_on_device, uint64_t text_bytes,
+                      const uint64_t *chunk_off, const uint64_t *chunk_len, uint32_t nchunks,
+                      uint32_t sample_bits, shk_batch_stats *stats, shk_sample_stats *sstats /* may be NULL */);
 
 /* ---- staged form of shk_count_words for several GPUs. The deNoise trigger is a property of
  * the WHOLE filter, so with quotient-range shards the host reduces each shard's statistics

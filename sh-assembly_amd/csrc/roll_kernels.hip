@@ -49,6 +49,9 @@ struct ShkRollArgs {
   // k_roll_scatter's split form only (partition_kernels.hip: the split record): key bits kept behind the first digit;
   // `out` then holds `cap` 4-byte words with `cap` bytes behind them
   uint32_t kb;
+  // k_roll_sample only: a k-mer is kept when bits [hb, hb + sample_bits) of its canonical hash are zero; cursor[0] = words
+  // reserved in `out` so far, cursor[1] = k-mers hashed, kept or not
+  uint32_t sample_bits;
 };
 
 // The two tables in LDS, indexed by the raw BYTE (no code lookup in between): row c of `in` = {seed[c], rol(seedc[c], k-1)},
@@ -538,4 +541,85 @@ __global__ void k_roll_slot_ends(const uint64_t *cursor, uint32_t P, uint64_t ca
   }
   const uint64_t tot = shk_block_sum64(s, scratch);
   if (threadIdx.x == 0) *nwords = tot;
+}
+
+// ---- sampling front end (shk_sample_chunks) ------------------------------------------------------------------------
+// The same k-mer stream once more, of which only a hash-chosen share leaves the kernel: a k-mer is KEPT when bits
+// [hb, hb + sample_bits) of its canonical hash are zero, and its key word (the hash's low hb bits, chunk tag 0) is appended
+// to a compacted list; every k-mer, kept or not, is counted. Whether a k-mer is kept depends on the k-mer alone, so the
+// table built from the list holds the exact abundances of a 2^-sample_bits share of the distinct k-mers. The bits sit
+// directly above the key bits: disjoint from the key, and clear of the hash's top bits, which are zero about twice as
+// often as they should be (the canonical hash is the smaller of two).
+// One thread per read and one round per thread and window, as in k_roll_scatter; shk_roll_round / shk_roll_round_pk run
+// with mask = ~0 and the emitter sees the whole hash. Kept keys wait in an LDS list PER WAVE: one LDS atomic per kept
+// key, one global atomic per FLUSH (cursor[0]), and nothing in the loop that a whole workgroup waits for -- the waves run
+// as freely as k_roll_hist's, which the kernel is measured against. (Per 832 M k-mers a form with one list per workgroup
+// and two LDS barriers per window took 1.79 ms at sample_bits = 8, this one 1.49; at 4, where the flushes' global atomics
+// on one address are what costs and a wave's list flushes four times as often as a workgroup's, 2.13 against 2.62: the
+// small samples of large inputs are what the kernel is for. DESIGN.md 7.) A wave's window appends at most WTILE = 64 x 16 keys
+// (sample_bits = 0: all of them), so a list of WTILE + WKEEP words that is flushed whenever it holds more than WKEEP
+// behind a window never overflows, and at sample_bits = 8 it is flushed every 64th window or so. Order inside the list
+// is free.
+template <int THREADS, int NQ>
+__global__ void __launch_bounds__(THREADS) k_roll_sample(ShkRollArgs A) {
+  constexpr uint32_t WAVES = THREADS / SHK_WAVE, WTILE = SHK_WAVE * SHK_ROLL_STEPS, WKEEP = WTILE / 4;
+  __shared__ ShkRollTabs T;
+  __shared__ uint64_t list[WAVES][WTILE + WKEEP];
+  __shared__ uint64_t scratch[SHK_MAX_WAVES + 1];
+  __shared__ uint64_t gbase[WAVES];
+  __shared__ uint32_t nlist[WAVES];
+  shk_roll_tabs_init(&T, A.k);
+  if (threadIdx.x < WAVES) nlist[threadIdx.x] = 0;
+  __syncthreads();
+  const uint32_t wave = shk_wave(), lane = shk_lane();
+  uint64_t *const wl = list[wave];
+  uint32_t *const wn = &nlist[wave];
+  const uint64_t nreads = *A.nreads_p;
+  const uint64_t kmask = (1ULL << A.hb) - 1;                  // (hb + sample_bits <= 56: the host's check)
+  const uint32_t smask = (1u << A.sample_bits) - 1, hb = A.hb;
+  const uint64_t stride = (uint64_t)gridDim.x * THREADS;
+  uint64_t r = (uint64_t)blockIdx.x * THREADS + threadIdx.x;
+  ShkRollState s;
+  s.st = 0; s.len = 0; s.i = 0; s.fill = 0; s.fh = 0; s.rh = 0;
+  uint64_t nk = 0;                 // k-mers this thread has hashed
+  bool have = false;
+  for (;;) {
+    // a thread whose read is used up takes its next one
+    while (!have && r < nreads) {
+      const uint64_t st = A.rd_start[r], en = A.rd_end[r];
+      if (en - st > 65535) atomicOr(A.err, SHK_E_BAD_FASTQ);                       // SHK_MAX_READ
+      if (en - st <= 65535 && en - st >= A.k) {
+        s.st = st; s.len = (uint32_t)(en - st); s.i = 0; s.fill = 0; s.fh = 0; s.rh = 0;
+        if (A.pk && !(A.pk_flag[r] >> 31)) s.st = A.pk_base[r] | (1ULL << 63);     // staged: its first unit instead of its text offset
+        have = true;
+      }
+      r += stride;
+    }
+    if (have) {
+      const auto keep = [&](int, uint64_t h) {
+        nk++;
+        if (!((uint32_t)(h >> hb) & smask)) wl[atomicAdd(wn, 1u)] = h & kmask;
+      };
+      have = (s.st >> 63) ? shk_roll_round_pk(&T, A.pk + (s.st & ~(1ULL << 63)), s, A.k, ~0ULL, keep)
+                          : shk_roll_round<NQ>(&T, A.text, A.safe_end, s, A.k, ~0ULL, keep);
+      if (have && s.i >= s.len) have = false;
+    }
+    const bool more = __ballot(have || r < nreads) != 0;      // (wave-uniform, like everything the wave decides below)
+    shk_wave_sync();
+    const uint32_t n = *wn;
+    shk_wave_sync();               // (every lane has read the count before the reset, or the next window's appends, change it)
+    if (n > WKEEP || (!more && n)) {
+      if (lane == 0) { gbase[wave] = atomicAdd((unsigned long long *)&A.cursor[0], (unsigned long long)n); *wn = 0; }
+      shk_wave_sync();
+      const uint64_t g = gbase[wave];
+      for (uint32_t i = lane; i < n; i += SHK_WAVE) {
+        const uint64_t at = g + i;
+        if (at < A.cap) A.out[at] = wl[i]; else atomicOr(A.err, SHK_E_KEYS_FULL);
+      }
+      shk_wave_sync();             // (the list is read out before the next window appends)
+    }
+    if (!more) break;
+  }
+  const uint64_t tot = shk_block_sum64(nk, scratch);
+  if (threadIdx.x == 0 && tot) atomicAdd((unsigned long long *)&A.cursor[1], (unsigned long long)tot);
 }

@@ -29,12 +29,12 @@
 
 enum {
   KP_COUNT_LINES, KP_SCAN_CHUNKS, KP_EMIT_READS, KP_COUNT_KEYS, KP_HASH, KP_SCAN, KP_RP_PREP, KP_RP_HIST,
-  KP_RP_SCATTER, KP_MERGE_SUM, KP_REGION_SCAN, KP_MERGE_WRITE, KP_MERGE_SPILL, KP_PLACE, KP_MARKS, KP_LOOKUP, KP_WALK, KP_UG_WALK, KP_UG_FINISH, KP_MERGE_FUSED, KP_MERGE_SAMPLE, KP_MISC, KP_ROLL_HIST, KP_ROLL_SCATTER, KP_PACK, KP_RP_SLOTS, KP_RP_SCATTER_NARROW, KP_SPECTRUM, KP_JOIN, KP_FA_MAPS, KP_FA_STATES, KP_FA_COUNT, KP_FA_COMPACT, KP_FA_SEGMENTS, KP_FA_PACK, KP_N
+  KP_RP_SCATTER, KP_MERGE_SUM, KP_REGION_SCAN, KP_MERGE_WRITE, KP_MERGE_SPILL, KP_PLACE, KP_MARKS, KP_LOOKUP, KP_WALK, KP_UG_WALK, KP_UG_FINISH, KP_MERGE_FUSED, KP_MERGE_SAMPLE, KP_MISC, KP_ROLL_HIST, KP_ROLL_SCATTER, KP_PACK, KP_RP_SLOTS, KP_RP_SCATTER_NARROW, KP_SPECTRUM, KP_JOIN, KP_FA_MAPS, KP_FA_STATES, KP_FA_COUNT, KP_FA_COMPACT, KP_FA_SEGMENTS, KP_FA_PACK, KP_ROLL_SAMPLE, KP_N
 };
 static const char *kp_names[KP_N] = {
   "k_count_lines", "k_scan_chunks", "k_emit_reads", "k_count_keys", "k_hash_reads", "k_scan_*", "k_rp_prep",
   "k_rp_hist", "k_rp_scatter", "k_region_merge<summary>", "k_region_scan", "k_region_merge<write>",
-  "k_region_merge<spill>", "k_region_place", "k_denoise_marks", "k_lookup", "k_extend_forward+k_select_seeds", "k_ug_walk", "k_ug_check/emit/median/links", "k_region_merge<fused>", "k_region_merge<sample>", "misc", "k_roll_hist", "k_roll_scatter", "k_pack_reads", "k_rp_slot_cursors", "k_rp_scatter<narrow>", "k_region_spectrum", "k_region_join", "k_fa_maps", "k_fa_states", "k_fa_count", "k_fa_compact", "k_fa_segments+long+tail", "k_fa_pack"};
+  "k_region_merge<spill>", "k_region_place", "k_denoise_marks", "k_lookup", "k_extend_forward+k_select_seeds", "k_ug_walk", "k_ug_check/emit/median/links", "k_region_merge<fused>", "k_region_merge<sample>", "misc", "k_roll_hist", "k_roll_scatter", "k_pack_reads", "k_rp_slot_cursors", "k_rp_scatter<narrow>", "k_region_spectrum", "k_region_join", "k_fa_maps", "k_fa_states", "k_fa_count", "k_fa_compact", "k_fa_segments+long+tail", "k_fa_pack", "k_roll_sample"};
 
 struct PendingEvent { int id; hipEvent_t a, b; };
 
@@ -54,6 +54,7 @@ enum ShkDevSlot {
   DS_WALK_OUT = 10,    // point_walk: ... and leaving it, 2 words
   DS_SPECTRUM = 12,    // shk_spectrum: the totals, SHK_SPEC_WORDS = 4 words
   DS_STAMPS = 16,      // SHK_STAMPS diagnostics: 16 words of cycle counts (ShkMergeArgs::dbg)
+  DS_SAMPLE = 32,      // shk_sample_chunks: k_roll_sample's two counters (words kept, k-mers hashed), 2 words
   DS_PAIR_LEN = 40,    // shk_stage_words_pair: lengths of the two sources, 2 words
   DS_PAIR_BASE = 42,   // shk_stage_words_pair: their one-bucket base arrays {0, na} and {0, nb}, 2 + 2 words
   DS_EXTENT = 46,      // a batch with slotted upper levels: positions (all slots) of the roll kernels' output, word 0, and of the
@@ -64,6 +65,7 @@ enum ShkDevSlot {
 enum ShkHostSlot {
   HP_COUNTERS = 0,     // merge_summary, point_read, merge2_run: d_counters, SHK_NCOUNTERS words (CNT_*, SHK_CNT_*)
   HP_SPECTRUM = 8,     // shk_spectrum: DS_SPECTRUM read back, 4 words
+  HP_SAMPLE = 12,      // shk_sample_chunks: DS_SAMPLE read back, 2 words
   HP_ERR = 40,         // err_enqueue / err_take: the error word (4 bytes)
   HP_NREADS = 41,      // parse_stage: DS_NREADS read back
   HP_NWORDS = 42,      // front_end, shk_hash_chunks: DS_NWORDS read back
@@ -84,6 +86,7 @@ enum { CNT_NEWD, CNT_ADDED, CNT_REMOVED, CNT_ADDED_BEFORE };   // counters[0..3]
 static_assert(HP_COUNTERS + SHK_NCOUNTERS <= HP_ERR, "the counters mirror ends before the error word");
 static_assert(HP_COUNTERS + SHK_NCOUNTERS <= HP_SPECTRUM && DS_SPECTRUM + (int)SHK_SPEC_WORDS <= DS_STAMPS, "the spectrum's totals have four words of their own");
 static_assert(DS_END <= SHK_SCALAR_WORDS && HP_END <= SHK_SCALAR_WORDS, "both blocks fit their 64 words");
+static_assert(DS_STAMPS + 16 <= DS_SAMPLE && DS_SAMPLE + 2 <= DS_PAIR_LEN && HP_SPECTRUM + (int)SHK_SPEC_WORDS <= HP_SAMPLE && HP_SAMPLE + 2 <= HP_ERR, "the sample counters have two words of their own");
 static_assert(DS_PAIR_BASE + 4 == DS_EXTENT && HP_PAIR + (DS_EXTENT - DS_PAIR_LEN) == HP_END, "the pair block is uploaded in one copy");
 
 // How a partition level runs, fixed by the geometry (create_init); a batch adds what its producer has counted already
@@ -677,7 +680,7 @@ static void roll_args(const shk_ctx *c, ShkStageBufs *b, ShkRollArgs &A, const u
   A.text = dtext; A.safe_end = (text_bytes + 15) & ~15ULL;
   A.rd_start = b->d_rd_start; A.rd_end = b->d_rd_end; A.nreads_p = b->d_scalars + DS_NREADS; A.rd_chunk = b->d_rd_chunk;
   A.chunk_first = chunk_first; A.chunk_mul = chunk_mul; A.k = c->cfg.k; A.hb = c->cfg.hb;
-  A.cap = c->cfg.max_batch_keys; A.err = b->d_err; A.kb = 0;
+  A.cap = c->cfg.max_batch_keys; A.err = b->d_err; A.kb = 0; A.sample_bits = 0;
 }
 // wide: A.hist_bits may exceed 10 (up to 14: two levels' digits together)
 static void launch_roll_hist(const shk_ctx *c, ShkStageBufs *b, const ShkRollArgs &A, uint64_t nreads, bool wide) {
@@ -1917,6 +1920,62 @@ extern "C" int shk_count_words(shk_ctx *c, const uint64_t *d_words, uint64_t nwo
   if (rc) return finish(c, rc);
   rc = merge_stage(c, c->d_words[dst], nchunks, nwords, &st);
   if (stats) *stats = st;
+  return finish(c, rc);
+}
+
+// ------------------------------------------------------------------ sampling front end (roll_kernels.hip: k_roll_sample)
+static void launch_roll_sample(const shk_ctx *c, ShkStageBufs *b, const ShkRollArgs &A, uint64_t nreads) {
+  ProfScope ps(c, b, KP_ROLL_SAMPLE);
+  if (c->threads >= 512) {
+    const uint64_t blocks = nreads / 256 + 1;
+    hipLaunchKernelGGL((k_roll_sample<256, 4>), dim3((uint32_t)(blocks < 1024 ? blocks : 1024)), dim3(256), 0, b->stream, A);
+  } else {          // (small workgroups: the CPU emulator build of the tests)
+    const uint64_t blocks = nreads / 64 + 1;
+    hipLaunchKernelGGL((k_roll_sample<64, 4>), dim3((uint32_t)(blocks < 64 ? blocks : 64)), dim3(64), 0, b->stream, A);
+  }
+}
+
+// The kept k-mers' key words go through the path of a caller's words (partition_words, merge_stage), so every geometry
+// works, the one-level contexts that have no roll path included.
+extern "C" int shk_sample_chunks(shk_ctx *c, const void *text, int text_on_device, uint64_t text_bytes,
+                                 const uint64_t *chunk_off, const uint64_t *chunk_len, uint32_t nchunks,
+                                 uint32_t sample_bits, shk_batch_stats *stats, shk_sample_stats *sstats) {
+  if (!c || !text) return SHK_ERR_ARG;
+  if (sample_bits > 24 || c->cfg.hb + sample_bits > 56 || c->cfg.num_shards > 1 || !text_aligned(text, text_on_device)) return SHK_ERR_ARG;
+  if (c->front && c->front->count) return SHK_ERR_BATCH;     // (their words are partitioned against the table as it is now)
+  if (!chunk_labels_ok(nchunks, 0, 1)) return SHK_ERR_BATCH;
+  if (!chunk_off || !chunk_len) return SHK_ERR_ARG;
+  shk_batch_stats st;
+  memset(&st, 0, sizeof(st));
+  HIPCHK(hipSetDevice(c->dev));
+  if (upload_wait(c, text, text_on_device, c->stream)) return SHK_ERR_HIP;
+  const uint8_t *dtext;
+  uint64_t nreads;
+  int rc = parse_stage(c, c, text, text_on_device, text_bytes, chunk_off, chunk_len, nchunks, &dtext, &nreads);
+  if (rc) return finish(c, rc);
+  ShkRollArgs A;
+  roll_args(c, c, A, dtext, text_bytes, 0, 1);
+  A.q_lo = c->q_lo; A.dig_shift = 0; A.dig_bits = 0; A.hist = nullptr; A.hist_shift = 0; A.hist_bits = 0;
+  A.cursor = c->d_scalars + DS_SAMPLE; A.out = c->d_words[0]; A.sample_bits = sample_bits;
+  HIPCHK(hipMemsetAsync(c->d_scalars + DS_SAMPLE, 0, 16, c->stream));
+  // (the 2-bit units lie in d_words[1] and are read for the last time before the partition starts)
+  rc = pack_stage(c, c, A, nreads, text_bytes, c->d_words[1]);
+  if (rc) return finish(c, rc);
+  launch_roll_sample(c, c, A, nreads);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(c->h_pinned + HP_SAMPLE, c->d_scalars + DS_SAMPLE, 16, hipMemcpyDeviceToHost, c->stream));
+  uint32_t bits = 0;
+  if (fetch_err(c, &bits)) { prof_collect(c); return SHK_ERR_HIP; }
+  const uint64_t kept = c->h_pinned[HP_SAMPLE], kmers = c->h_pinned[HP_SAMPLE + 1];
+  if (bits) { prof_collect(c); return map_err_bits(bits); }
+  if (kept > c->cfg.max_batch_keys) { prof_collect(c); return SHK_ERR_BATCH; }
+  int dst = 0;
+  rc = partition_words(c, c->d_words[0], kept, &dst);
+  if (rc) return finish(c, rc);
+  // to the table the call is one chunk: the trigger is tested once, behind it
+  rc = merge_stage(c, c->d_words[dst], 1, kept, &st);
+  if (stats) *stats = st;
+  if (sstats) { sstats->kmers = kmers; sstats->kept = kept; }
   return finish(c, rc);
 }
 

@@ -53,6 +53,14 @@ class FastaStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class SampleStats(C.Structure):
+    """shk_sample_stats (include/shk.h)"""
+    _fields_ = [("kmers", C.c_uint64), ("kept", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class Summary(C.Structure):
     _fields_ = [("new_distinct", C.c_uint64), ("added", C.c_uint64), ("removed", C.c_uint64),
                 ("err_bits", C.c_uint32), ("reserved", C.c_uint32)]
@@ -84,7 +92,7 @@ EXPORTS = ["shk_create", "shk_destroy", "shk_count_chunks", "shk_hash_chunks", "
            "shk_stats", "shk_header", "shk_export_blocks", "shk_export_cqf", "shk_import_cqf", "shk_import_blocks",
            "shk_lookup", "shk_profile_enable", "shk_profile_get", "shk_profile_reset", "shk_strerror",
            "shk_last_error_bits", "shk_insert_counted", "shk_dump", "shk_merge", "shk_multi_merge", "shk_import_shards", "shk_table_ptr", "shk_unitigs_add_reads",
-           "shk_spectrum", "shk_inner_product", "shk_magnitude", "shk_intersect", "shk_count_fasta", "shk_split_batches"]
+           "shk_spectrum", "shk_inner_product", "shk_magnitude", "shk_intersect", "shk_count_fasta", "shk_split_batches", "shk_sample_chunks"]
 
 _libs = {}
 
@@ -104,6 +112,7 @@ def load(path=None):
     L.shk_destroy.restype = None
     L.shk_count_chunks.argtypes = [vp, vp, i32, u64, pu64, pu64, u32, C.POINTER(BatchStats)]
     L.shk_count_fasta.argtypes = [vp, vp, i32, u64, i32, C.POINTER(BatchStats), C.POINTER(FastaStats)]
+    L.shk_sample_chunks.argtypes = [vp, vp, i32, u64, pu64, pu64, u32, u32, C.POINTER(BatchStats), C.POINTER(SampleStats)]
     L.shk_hash_chunks.argtypes = [vp, vp, i32, u64, pu64, pu64, u32, C.POINTER(vp), pu64]
     L.shk_upload_text.argtypes = [vp, vp, u64, C.POINTER(vp)]
     L.shk_count_words.argtypes = [vp, vp, u64, u32, C.POINTER(BatchStats)]
@@ -269,6 +278,19 @@ class Context:
             ptr, n = C.cast(buf, C.c_void_p), len(text)
         self._chk(self.L.shk_count_fasta(self.h, ptr, 1 if on_device else 0, n, 1 if first else 0, C.byref(st), C.byref(fs)))
         return st.as_dict(), fs.as_dict()
+
+    def sample_chunks(self, text, chunk_off, chunk_len, sample_bits, on_device=False, text_bytes=None):
+        """count the k-mers whose canonical hash has bits [hb, hb + sample_bits) zero (shk_sample_chunks); text as in
+        count_chunks. Returns (batch statistics, sample statistics) as dicts."""
+        st, ss = BatchStats(), SampleStats()
+        if on_device or isinstance(text, int):
+            ptr, n = C.c_void_p(int(text)), int(text_bytes)
+        else:
+            buf = (C.c_char * max(len(text), 1)).from_buffer_copy(bytes(text) or b"\0") if not isinstance(text, C.Array) else text
+            ptr, n = C.cast(buf, C.c_void_p), len(text)
+        self._chk(self.L.shk_sample_chunks(self.h, ptr, 1 if on_device else 0, n, self._tab(chunk_off), self._tab(chunk_len),
+                                           len(chunk_off), int(sample_bits), C.byref(st), C.byref(ss)))
+        return st.as_dict(), ss.as_dict()
 
     def upload_text(self, host_ptr, nbytes):
         """start the copy of host text for a later count_chunks(..., on_device=True); returns the device pointer"""
