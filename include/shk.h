@@ -33,6 +33,8 @@
  *   shk_magnitude         qf_magnitude                                      cqf/gqf.c:2760-2763
  *   shk_spectrum          (no counterpart: the reference's README sends the user to an outside program for F0, F1, f1, f2, ...)
  *   shk_count_fasta       (no counterpart: the reference reads 4-line FASTQ only, cqf/CQF_mt.h:610-731) FASTA text of any shape
+ *   shk_query_fasta       (no counterpart: the reference answers one hashed key at a time, qf_count_key_value) FASTA text against
+ *                         the table: per-base counts and per-record totals
  *   shk_sample_chunks     (no counterpart: the reference's README sends the user to ntCard) -N -n -e from the reads themselves
  *   shk_import_shards     (no counterpart: the reference is one process) quotient-range shards -> the single table
  *   shk_stats             runtime->nelts / ndistinct_elts / num_deNoise    cqf/CQF_mt.h:277-288
@@ -204,6 +206,43 @@ int shk_count_words(shk_ctx *ctx, const uint64_t *d_words, uint64_t nwords, uint
 typedef struct shk_fasta_stats { uint64_t records, bases, breaks, kmers; } shk_fasta_stats;
 int shk_count_fasta(shk_ctx *ctx, const void *text, int text_on_device, uint64_t text_bytes, int first,
                     shk_batch_stats *stats, shk_fasta_stats *fstats /* may be NULL */);
+
+/* ---- FASTA text against the table (no counterpart in the reference): how often does the table hold the k-mers of this
+ * sequence, position by position and record by record? One streamed pass; the table stays untouched.
+ *   - Grammar and k-mers: exactly shk_count_fasta's (header lines, breaks, runs, both cases, '\r', no limit on line or
+ *     record length); a k-mer's key is the one the counting paths give it. 1 <= k <= 191, every geometry.
+ *   - Streaming: consecutive calls are consecutive pieces of ONE stream, cut at any byte; first != 0 starts a new stream.
+ *     A k-mer is answered by the call that brings its last base. The query stream keeps its own state (line state, pending
+ *     break, the tail of <= k - 1 bases on the device), apart from shk_count_fasta's: count calls and query calls on one
+ *     context may interleave without seeing each other.
+ *   - track (may be NULL; a host pointer unless track_on_device != 0): for b in [0, bases of this piece), track[b] belongs to
+ *     the k-mer whose last base is the piece's b-th base in text order (bytes that are no bases do not count). Its value is
+ *     that k-mer's count in the table, capped at 0xFFFFFFFE, or SHK_QUERY_NONE where no k-mer ends (fewer than k bases lie
+ *     behind the last break). The tracks of a stream's pieces, concatenated, are the track of the text in one call. With
+ *     track == NULL the call allocates and writes no per-base buffer at all.
+ *   - rec (may be NULL; host memory): rec[0] belongs to the record that was open when the piece began (or to text in front
+ *     of any header), rec[i], i >= 1, to the i-th header line begun in this piece; *nrec = 1 + records. Each entry holds,
+ *     over the k-mers of that record answered by this call: kmers = their number, present = those with count >= 1, solid =
+ *     those with count >= min_count, sum = their true (uncapped) counts mod 2^64. A run never crosses a header, so every
+ *     k-mer has exactly one record. A caller adds rec[0] to the last record it already has.
+ *   - qstats (may be NULL): the same four sums over the whole piece; records, bases, breaks and kmers mean what
+ *     shk_fasta_stats means by them.
+ *   - It is a reader: it launches the pending lazy placement first, as shk_lookup does, reads with mark mode 2 (traveled
+ *     bits are neither read nor set), and changes no byte of the table and no runtime counter.
+ * Errors leave the query stream's state as it was: SHK_ERR_ARG for a sharded context or device text that is not 16-byte
+ * aligned; SHK_ERR_BATCH for text_bytes > max_batch_bytes, the capacity limits shk_count_fasta states (the call borrows the
+ * same batch buffers), batches prepared and not yet counted, track_cap smaller than the piece's bases, or rec_cap <
+ * 1 + records -- *nrec is then still set to the number needed, so the call can be repeated.
+ * Besides shk_count_fasta's buffers a context that has answered queries keeps 40 bytes per record of the piece with the
+ * most records so far and, for host tracks, 4 bytes per base of the piece with the most bases so far. */
+#define SHK_QUERY_NONE 0xFFFFFFFFu
+typedef struct shk_query_record { uint64_t kmers, present, solid, sum; } shk_query_record;
+typedef struct shk_query_stats  { uint64_t records, bases, breaks, kmers, present, solid, sum; } shk_query_stats;
+int shk_query_fasta(shk_ctx *ctx, const void *text, int text_on_device, uint64_t text_bytes, int first,
+                    uint32_t min_count,
+                    uint32_t *track, uint64_t track_cap, int track_on_device,      /* track may be NULL */
+                    shk_query_record *rec, uint32_t rec_cap, uint32_t *nrec,       /* rec may be NULL; host memory */
+                    shk_query_stats *qstats /* may be NULL */);
 
 /* ---- a hash-sampled spectrum of the reads (no counterpart in the reference, whose README sends the user to ntCard for
  * the -N -n -e its command line wants). Hashes every k-mer of the FASTQ chunks exactly as shk_count_chunks does (the

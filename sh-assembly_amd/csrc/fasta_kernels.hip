@@ -66,6 +66,7 @@ __device__ __forceinline__ ShkFaMasks shk_fa_masks(const ShkQuad &v, uint32_t nv
 struct ShkFaWalk {
   uint32_t nbase, nbreak, nrec;   // bases, break bytes, header lines begun
   uint32_t basemask, startmask;   // bytes that are bases; those of them that open a run
+  uint32_t openmask;              // first bytes of the header lines begun (query_kernels.hip: the records' starts)
 };
 // The bytes behind M from state st on; returns the state behind them. All 16 bytes at once, on the masks:
 //   header bytes   a header opens at a line start (behind a line feed, or byte 0 in state "line start") that holds '>' or
@@ -77,7 +78,7 @@ struct ShkFaWalk {
 //                  carries each break through the gap behind it onto the next event.
 __device__ __forceinline__ uint32_t shk_fa_walk(const ShkFaMasks &M, uint32_t st, ShkFaWalk *out) {
   const uint32_t ls = st >> 1, pend = st & 1u;
-  ShkFaWalk r = {0, 0, 0, 0, 0};
+  ShkFaWalk r = {0, 0, 0, 0, 0, 0};
   *out = r;
   if (!M.valid) return st;
   const uint32_t opens = ((M.nl << 1) | (uint32_t)(ls == 1)) & M.hd;
@@ -86,7 +87,7 @@ __device__ __forceinline__ uint32_t shk_fa_walk(const ShkFaMasks &M, uint32_t st
   const uint32_t e = seq & M.base, b = seq & ~M.base, bev = b | opens, ev = e | bev;
   const uint32_t gaps = ~ev & 0x1FFFFu;
   r.nbase = (uint32_t)__popc(e); r.nbreak = (uint32_t)__popc(b); r.nrec = (uint32_t)__popc(opens);
-  r.basemask = e;
+  r.basemask = e; r.openmask = opens;
   r.startmask = (((bev << 1) | pend) + gaps) & e;
   *out = r;
   const uint32_t last = M.valid ^ (M.valid >> 1);      // the last byte
@@ -168,8 +169,9 @@ __global__ void __launch_bounds__(1024) k_fa_states(const uint32_t *tile_map, ui
   if (threadIdx.x == blockDim.x - 1) *end_state = s;
 }
 
+// tile_rec (null: not wanted) = the header lines begun in every tile, for the scan of shk_query_fasta's record starts
 __global__ void __launch_bounds__(256) k_fa_count(const uint8_t *text, uint64_t n, uint64_t safe_end, const uint32_t *tile_state, uint8_t *unit_state,
-                                                   uint64_t *tile_cnt, uint64_t *counters) {
+                                                   uint64_t *tile_cnt, uint64_t *counters, uint64_t *tile_rec) {
   __shared__ uint32_t arr[SHK_MAX_WAVES];
   __shared__ uint64_t scratch[SHK_MAX_WAVES + 1];
   uint32_t nvalid, ex;
@@ -186,6 +188,7 @@ __global__ void __launch_bounds__(256) k_fa_count(const uint8_t *text, uint64_t 
     tile_cnt[blockIdx.x] = (tot & 0xFFFFu) | ((tot >> 16) & 0xFFFFu) << SHK_FA_COUNT_BITS;
     if ((tot >> 32) & 0xFFFFu) atomicAdd((unsigned long long *)&counters[FA_NBREAK], (unsigned long long)((tot >> 32) & 0xFFFFu));
     if (tot >> 48) atomicAdd((unsigned long long *)&counters[FA_NREC], (unsigned long long)(tot >> 48));
+    if (tile_rec) tile_rec[blockIdx.x] = tot >> 48;
   }
 }
 
@@ -198,7 +201,7 @@ __global__ void __launch_bounds__(256) k_fa_compact(const uint8_t *text, uint64_
   __shared__ uint32_t scratch[SHK_MAX_WAVES + 1];
   uint32_t nvalid, tot;
   const ShkQuad v = shk_fa_load(text, n, safe_end, &nvalid);
-  ShkFaWalk w = {0, 0, 0, 0, 0};
+  ShkFaWalk w = {0, 0, 0, 0, 0, 0};
   if (nvalid) shk_fa_walk(shk_fa_masks(v, nvalid), unit_state[(uint64_t)blockIdx.x * blockDim.x + threadIdx.x], &w);
   const uint32_t ex = shk_block_exscan(w.nbase | (uint32_t)__popc(w.startmask) << 16, &tot, scratch);
   if (blockIdx.x == 0 && threadIdx.x == 0) {

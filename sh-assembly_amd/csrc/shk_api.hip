@@ -24,17 +24,18 @@
 #include "walk_kernels.hip"
 #include "unitig_kernels.hip"
 #include "fasta_kernels.hip"
+#include "query_kernels.hip"
 
 #define SHK_SLACK 256  // bytes of slack behind buffers read with wide loads
 
 enum {
   KP_COUNT_LINES, KP_SCAN_CHUNKS, KP_EMIT_READS, KP_COUNT_KEYS, KP_HASH, KP_SCAN, KP_RP_PREP, KP_RP_HIST,
-  KP_RP_SCATTER, KP_MERGE_SUM, KP_REGION_SCAN, KP_MERGE_WRITE, KP_MERGE_SPILL, KP_PLACE, KP_MARKS, KP_LOOKUP, KP_WALK, KP_UG_WALK, KP_UG_FINISH, KP_MERGE_FUSED, KP_MERGE_SAMPLE, KP_MISC, KP_ROLL_HIST, KP_ROLL_SCATTER, KP_PACK, KP_RP_SLOTS, KP_RP_SCATTER_NARROW, KP_SPECTRUM, KP_JOIN, KP_FA_MAPS, KP_FA_STATES, KP_FA_COUNT, KP_FA_COMPACT, KP_FA_SEGMENTS, KP_FA_PACK, KP_ROLL_SAMPLE, KP_N
+  KP_RP_SCATTER, KP_MERGE_SUM, KP_REGION_SCAN, KP_MERGE_WRITE, KP_MERGE_SPILL, KP_PLACE, KP_MARKS, KP_LOOKUP, KP_WALK, KP_UG_WALK, KP_UG_FINISH, KP_MERGE_FUSED, KP_MERGE_SAMPLE, KP_MISC, KP_ROLL_HIST, KP_ROLL_SCATTER, KP_PACK, KP_RP_SLOTS, KP_RP_SCATTER_NARROW, KP_SPECTRUM, KP_JOIN, KP_FA_MAPS, KP_FA_STATES, KP_FA_COUNT, KP_FA_COMPACT, KP_FA_SEGMENTS, KP_FA_PACK, KP_ROLL_SAMPLE, KP_ROLL_QUERY, KP_FA_REC_STARTS, KP_N
 };
 static const char *kp_names[KP_N] = {
   "k_count_lines", "k_scan_chunks", "k_emit_reads", "k_count_keys", "k_hash_reads", "k_scan_*", "k_rp_prep",
   "k_rp_hist", "k_rp_scatter", "k_region_merge<summary>", "k_region_scan", "k_region_merge<write>",
-  "k_region_merge<spill>", "k_region_place", "k_denoise_marks", "k_lookup", "k_extend_forward+k_select_seeds", "k_ug_walk", "k_ug_check/emit/median/links", "k_region_merge<fused>", "k_region_merge<sample>", "misc", "k_roll_hist", "k_roll_scatter", "k_pack_reads", "k_rp_slot_cursors", "k_rp_scatter<narrow>", "k_region_spectrum", "k_region_join", "k_fa_maps", "k_fa_states", "k_fa_count", "k_fa_compact", "k_fa_segments+long+tail", "k_fa_pack", "k_roll_sample"};
+  "k_region_merge<spill>", "k_region_place", "k_denoise_marks", "k_lookup", "k_extend_forward+k_select_seeds", "k_ug_walk", "k_ug_check/emit/median/links", "k_region_merge<fused>", "k_region_merge<sample>", "misc", "k_roll_hist", "k_roll_scatter", "k_pack_reads", "k_rp_slot_cursors", "k_rp_scatter<narrow>", "k_region_spectrum", "k_region_join", "k_fa_maps", "k_fa_states", "k_fa_count", "k_fa_compact", "k_fa_segments+long+tail", "k_fa_pack", "k_roll_sample", "k_roll_query", "k_fa_rec_starts"};
 
 struct PendingEvent { int id; hipEvent_t a, b; };
 
@@ -209,7 +210,7 @@ struct shk_ctx : ShkStageBufs {
   uint64_t *d_send[2];          // shk_route_words: two alternating send buffers (allocated on first use), so that the
   int send_next;                // exchange of one batch can run while the next batch is hashed and routed
   struct ShkFront *front;       // shk_prepare_chunks: the front end (parse, hash, partition) of later batches on its own stream
-  struct ShkFasta *fasta;       // shk_count_fasta: its buffers and the state of the stream (allocated by the first call)
+  struct ShkFasta *fasta;       // shk_count_fasta, shk_query_fasta: their buffers and the states of their streams (allocated by the first call)
   uint32_t fasta_seg;           // k-mers per segment there (SHK_FASTA_SEGMENT)
 };
 
@@ -1993,11 +1994,21 @@ struct ShkFasta {
   uint64_t cap_long = 0;
   uint64_t *counters = nullptr;     // [FA_NCOUNTERS] on the device
   uint64_t *h = nullptr;            // pinned: [0, FA_NCOUNTERS) the counters read back, [FA_NCOUNTERS] the scan's total
-  ShkQuad *tail[2] = {};            // the open run's last <= k - 1 bases (three units); tail[cur] is the committed one
-  int cur = 0;
-  uint32_t state = SHK_FA_STATE_START;
-  uint64_t tail_len = 0;
+  // Two streams of pieces that do not see each other: [0] shk_count_fasta's, [1] shk_query_fasta's
+  struct Stream {
+    ShkQuad *tail[2] = {};          // the open run's last <= k - 1 bases (three units); tail[cur] is the committed one
+    int cur = 0;
+    uint32_t state = SHK_FA_STATE_START;
+    uint64_t tail_len = 0;
+  } s[2];
+  // shk_query_fasta only
+  uint64_t *tile_rec = nullptr, *rec_off = nullptr;   // header lines begun per tile, and their scan
+  uint64_t *q_rec = nullptr;        // the piece's records: four sums each (record 0 = the one open when the piece began), then
+  uint64_t q_rec_cap = 0;           // their first base ordinals; grown to the most records a piece has had
+  uint32_t *q_track = nullptr;      // a host caller's track, grown to the most bases a piece with a track has had
+  uint64_t q_track_cap = 0;
 };
+enum { FA_COUNT_STREAM = 0, FA_QUERY_STREAM = 1 };
 static uint32_t fasta_threads(const shk_ctx *c) { return c->threads < 256 ? c->threads : 256; }
 static void fasta_destroy(shk_ctx *c);
 static int fasta_alloc(shk_ctx *c);
@@ -2013,8 +2024,10 @@ static int fasta_alloc(shk_ctx *c) {
   const uint64_t nb = c->cfg.max_batch_bytes, ntiles = nb / (16 * fasta_threads(c)) + 2;
   F->stream_words = (nb + 192) / 16 + 16;     // (two quads of room behind the last base: shk_fa_unit loads a unit's neighbour)
   if (dmalloc(&F->stream, F->stream_words) || dmalloc(&F->unit_state, nb / 16 + 2) || dmalloc(&F->tile_map, ntiles) || dmalloc(&F->tile_state, ntiles) ||
-      dmalloc(&F->tile_cnt, ntiles) || dmalloc(&F->tile_off, ntiles + 1) || dmalloc(&F->counters, FA_NCOUNTERS) || dmalloc(&F->tail[0], 3) ||
-      dmalloc(&F->tail[1], 3)) return SHK_ERR_HIP;
+      dmalloc(&F->tile_cnt, ntiles) || dmalloc(&F->tile_off, ntiles + 1) || dmalloc(&F->counters, FA_NCOUNTERS) || dmalloc(&F->tile_rec, ntiles) ||
+      dmalloc(&F->rec_off, ntiles + 1)) return SHK_ERR_HIP;
+  for (int i = 0; i < 2; i++)
+    if (dmalloc(&F->s[i].tail[0], 3) || dmalloc(&F->s[i].tail[1], 3)) return SHK_ERR_HIP;
   F->cap_long = ntiles;
   if (dmalloc(&F->long_runs, SHK_FA_LONG_WORDS * F->cap_long)) return SHK_ERR_HIP;
   HIPCHK(hipHostMalloc((void **)&F->h, (FA_NCOUNTERS + 1) * sizeof(uint64_t), hipHostMallocDefault));
@@ -2025,7 +2038,8 @@ static void fasta_destroy(shk_ctx *c) {
   if (!F) return;
   if (c->stream) hipStreamSynchronize(c->stream);
   hipFree(F->stream); hipFree(F->unit_state); hipFree(F->tile_map); hipFree(F->tile_state); hipFree(F->tile_cnt); hipFree(F->tile_off);
-  hipFree(F->counters); hipFree(F->tail[0]); hipFree(F->tail[1]); hipFree(F->long_runs);
+  hipFree(F->counters); hipFree(F->long_runs); hipFree(F->tile_rec); hipFree(F->rec_off); hipFree(F->q_rec); hipFree(F->q_track);
+  for (int i = 0; i < 2; i++) { hipFree(F->s[i].tail[0]); hipFree(F->s[i].tail[1]); }
   hipHostFree(F->h);
   delete F;
   c->fasta = nullptr;
@@ -2062,19 +2076,24 @@ static int fasta_keys(shk_ctx *c, uint64_t nseg, uint64_t nkmers, int *dst) {
   return partition_stage(c, c, part_from_words(c, c->d_words[0], nkmers), dst);
 }
 
-extern "C" int shk_count_fasta(shk_ctx *c, const void *text, int text_on_device, uint64_t text_bytes, int first,
-                               shk_batch_stats *stats, shk_fasta_stats *fstats) {
-  if (!c || (!text && text_bytes) || c->cfg.num_shards > 1 || !text_aligned(text, text_on_device)) return SHK_ERR_ARG;
-  if (c->front && c->front->count) return SHK_ERR_BATCH;     // (their words are partitioned against the table as it is now)
-  if (text_bytes > c->cfg.max_batch_bytes) return SHK_ERR_BATCH;
-  shk_batch_stats st;
-  memset(&st, 0, sizeof(st));
-  HIPCHK(hipSetDevice(c->dev));
-  if (upload_wait(c, text, text_on_device, c->stream)) return SHK_ERR_HIP;
-  { int rc = fasta_init(c); if (rc) return rc; }
+// What shk_query_fasta wants of the front end besides the segments (null: shk_count_fasta)
+struct ShkFaQuery {
+  bool want_track; uint64_t track_cap;
+  bool want_rec; uint32_t rec_cap; uint32_t *nrec_out;
+};
+// One piece of a stream through the front end
+struct ShkFaPiece {
+  uint64_t tail, nbases, nbreaks, nrec, nseg, nkmers, new_tail;
+  uint32_t end_state;
+};
+// Stages (a) to (d) of a piece of stream S: classes, stream and run list, segments and their 2-bit units, the new tail
+// (written to the stream's spare tail buffer: the caller commits it, with P's end state, once the piece has been taken).
+// Leaves the segments as staged reads: the read arrays, d_key_base, d_nkeys, and the units in d_words[1].
+static int fasta_front(shk_ctx *c, ShkFasta::Stream *S, const void *text, int text_on_device, uint64_t text_bytes, int first, const ShkFaQuery *Q,
+                       ShkFaPiece *P) {
   ShkFasta *F = c->fasta;
-  const uint32_t st0 = first ? SHK_FA_STATE_START : F->state, k = c->cfg.k, t = fasta_threads(c);
-  const uint64_t tail = first ? 0 : F->tail_len;
+  const uint32_t st0 = first ? SHK_FA_STATE_START : S->state, k = c->cfg.k, t = fasta_threads(c);
+  const uint64_t tail = first ? 0 : S->tail_len;
   const uint8_t *dtext = (const uint8_t *)text;
   if (!text_on_device && text_bytes) {
     HIPCHK(hipMemcpyAsync(c->d_text, text, text_bytes, hipMemcpyHostToDevice, c->stream));
@@ -2090,36 +2109,54 @@ extern "C" int shk_count_fasta(shk_ctx *c, const void *text, int text_on_device,
     hipLaunchKernelGGL(k_fa_states, dim3(1), dim3(c->threads), 0, c->stream, (const uint32_t *)F->tile_map, ntiles, st0, F->tile_state, F->counters + FA_END_STATE); }
   if (ntiles) { ProfScope ps(c, KP_FA_COUNT);
     hipLaunchKernelGGL(k_fa_count, tiles, dim3(t), 0, c->stream, dtext, text_bytes, safe_end, (const uint32_t *)F->tile_state, F->unit_state,
-                       F->tile_cnt, F->counters); }
+                       F->tile_cnt, F->counters, Q ? F->tile_rec : (uint64_t *)nullptr); }
   if (run_scan<uint64_t>(c, c, F->tile_cnt, ntiles, nullptr, F->tile_off)) return SHK_ERR_HIP;
+  // (the header lines per tile need a scan of their own: the tile word's 36 + 28 bits are taken)
+  if (Q && run_scan<uint64_t>(c, c, F->tile_rec, ntiles, nullptr, F->rec_off)) return SHK_ERR_HIP;
   HIPCHK(hipMemcpyAsync(F->h, F->counters, FA_NCOUNTERS * 8, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipMemcpyAsync(F->h + FA_NCOUNTERS, F->tile_off + ntiles, 8, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   const uint64_t nbases = F->h[FA_NCOUNTERS] & SHK_FA_COUNT_MASK, nruns = 1 + (F->h[FA_NCOUNTERS] >> SHK_FA_COUNT_BITS);
-  const uint64_t nbreaks = F->h[FA_NBREAK], nrec = F->h[FA_NREC];
+  const uint64_t nrec = F->h[FA_NREC];
   const uint32_t end_state = (uint32_t)F->h[FA_END_STATE];
+  P->tail = tail; P->nbases = nbases; P->nbreaks = F->h[FA_NBREAK]; P->nrec = nrec; P->end_state = end_state;
   const uint64_t cap_runs = words_cap(c), cap_units = c->cfg.max_batch_keys / 2 > 1 ? c->cfg.max_batch_keys / 2 - 1 : 0;
   if (nruns + 1 > cap_runs) { prof_collect(c); return SHK_ERR_BATCH; }
+  if (Q) {
+    // what the caller's arrays must hold is known here, before anything of the stream's has moved
+    if (nrec + 1 > 0xFFFFFFFFull) { prof_collect(c); return SHK_ERR_BATCH; }
+    if (Q->nrec_out) *Q->nrec_out = (uint32_t)(nrec + 1);
+    if ((Q->want_track && Q->track_cap < nbases) || (Q->want_rec && Q->rec_cap < nrec + 1)) { prof_collect(c); return SHK_ERR_BATCH; }
+    if (nrec + 1 > F->q_rec_cap) {
+      hipFree(F->q_rec); F->q_rec = nullptr; F->q_rec_cap = 0;
+      const uint64_t want = nrec + 1 + (nrec + 1) / 2;
+      if (dmalloc(&F->q_rec, 5 * want)) { prof_collect(c); return SHK_ERR_HIP; }
+      F->q_rec_cap = want;
+    }
+    if (nrec) { ProfScope ps(c, KP_FA_REC_STARTS);
+      hipLaunchKernelGGL(k_fa_rec_starts, tiles, dim3(t), 0, c->stream, dtext, text_bytes, safe_end, (const uint8_t *)F->unit_state, (const uint64_t *)F->tile_off,
+                         (const uint64_t *)F->rec_off, ntiles, tail, F->q_rec + 4 * (nrec + 1), nrec); }
+  }
   // (b) the stream and the run list, (c) the segments, (d) the tail
   uint64_t *run_start = c->d_words[0];
   { const uint64_t used = ((tail + nbases + 15) / 16 + 12) * 4;
     HIPCHK(hipMemsetAsync(F->stream, 0, used < F->stream_words * 4 ? used : F->stream_words * 4, c->stream));
-    if (tail) HIPCHK(hipMemcpyAsync(F->stream, F->tail[F->cur], 48, hipMemcpyDeviceToDevice, c->stream)); }
-  ShkFaSegArgs S;
-  S.run_start = run_start; S.nruns = nruns; S.k = k; S.seg = c->fasta_seg;
-  S.rd_start = c->d_rd_start; S.rd_end = c->d_rd_end; S.rd_chunk = c->d_rd_chunk; S.flag = c->d_nkeys; S.pk_base = c->d_key_base;
-  S.cap_seg = c->max_reads; S.cap_units = cap_units; S.long_runs = F->long_runs; S.cap_long = F->cap_long; S.counters = F->counters; S.err = c->d_err;
-  uint64_t nseg = 0, nkmers = 0;
+    if (tail) HIPCHK(hipMemcpyAsync(F->stream, S->tail[S->cur], 48, hipMemcpyDeviceToDevice, c->stream)); }
+  ShkFaSegArgs G;
+  G.run_start = run_start; G.nruns = nruns; G.k = k; G.seg = c->fasta_seg;
+  G.rd_start = c->d_rd_start; G.rd_end = c->d_rd_end; G.rd_chunk = c->d_rd_chunk; G.flag = c->d_nkeys; G.pk_base = c->d_key_base;
+  G.cap_seg = c->max_reads; G.cap_units = cap_units; G.long_runs = F->long_runs; G.cap_long = F->cap_long; G.counters = F->counters; G.err = c->d_err;
   { ProfScope ps(c, KP_FA_COMPACT);
     hipLaunchKernelGGL(k_fa_compact, tiles, dim3(t), 0, c->stream, dtext, text_bytes, safe_end, (const uint8_t *)F->unit_state, (const uint64_t *)F->tile_off,
                        ntiles, tail, F->stream, F->stream_words, run_start, cap_runs, c->d_err); }
   { ProfScope ps(c, KP_FA_SEGMENTS);
     const uint64_t blocks = nruns / t + 1;
-    hipLaunchKernelGGL(k_fa_segments, dim3((uint32_t)(blocks < 2048 ? blocks : 2048)), dim3(t), 0, c->stream, S);
-    hipLaunchKernelGGL(k_fa_long_segments, dim3(c->threads < 512 ? 2 : 512), dim3(t), 0, c->stream, S);     // (small workgroups: the CPU emulator build of the tests)
+    hipLaunchKernelGGL(k_fa_segments, dim3((uint32_t)(blocks < 2048 ? blocks : 2048)), dim3(t), 0, c->stream, G);
+    hipLaunchKernelGGL(k_fa_long_segments, dim3(c->threads < 512 ? 2 : 512), dim3(t), 0, c->stream, G);     // (small workgroups: the CPU emulator build of the tests)
     hipLaunchKernelGGL(k_fa_tail, dim3(1), dim3(64), 0, c->stream, (const uint32_t *)F->stream, (const uint64_t *)run_start, nruns, end_state, k,
-                       F->tail[F->cur ^ 1], F->counters); }
+                       S->tail[S->cur ^ 1], F->counters); }
   HIPCHK(hipMemcpyAsync(F->h, F->counters, FA_NCOUNTERS * 8, hipMemcpyDeviceToHost, c->stream));
+  uint64_t nseg = 0, nkmers = 0;
   { uint32_t bits = 0;
     if (fetch_err(c, &bits)) return SHK_ERR_HIP;
     nseg = F->h[FA_NSEG]; nkmers = F->h[FA_NKMERS];
@@ -2132,19 +2169,95 @@ extern "C" int shk_count_fasta(shk_ctx *c, const void *text, int text_on_device,
                        (const uint64_t *)c->d_rd_end, (const uint64_t *)c->d_key_base, (const uint32_t *)c->d_nkeys, (ShkQuad *)c->d_words[1], cap_units, c->d_err);
   }
   HIPCHK(hipGetLastError());
-  const uint64_t new_tail = F->h[FA_TAIL_LEN];
+  P->nseg = nseg; P->nkmers = nkmers; P->new_tail = F->h[FA_TAIL_LEN];
+  return SHK_OK;
+}
+
+extern "C" int shk_count_fasta(shk_ctx *c, const void *text, int text_on_device, uint64_t text_bytes, int first,
+                               shk_batch_stats *stats, shk_fasta_stats *fstats) {
+  if (!c || (!text && text_bytes) || c->cfg.num_shards > 1 || !text_aligned(text, text_on_device)) return SHK_ERR_ARG;
+  if (c->front && c->front->count) return SHK_ERR_BATCH;     // (their words are partitioned against the table as it is now)
+  if (text_bytes > c->cfg.max_batch_bytes) return SHK_ERR_BATCH;
+  shk_batch_stats st;
+  memset(&st, 0, sizeof(st));
+  HIPCHK(hipSetDevice(c->dev));
+  if (upload_wait(c, text, text_on_device, c->stream)) return SHK_ERR_HIP;
+  { int rc = fasta_init(c); if (rc) return rc; }
+  ShkFasta::Stream *S = &c->fasta->s[FA_COUNT_STREAM];
+  ShkFaPiece P;
+  { int rc = fasta_front(c, S, text, text_on_device, text_bytes, first, nullptr, &P); if (rc) return rc; }
   int dst = 0;
-  int rc = fasta_keys(c, nseg, nkmers, &dst);
+  int rc = fasta_keys(c, P.nseg, P.nkmers, &dst);
   if (rc) return finish(c, rc);
   // to the table the piece is one chunk: the trigger is tested once, behind it
-  rc = merge_stage(c, c->d_words[dst], 1, nkmers, &st);
+  rc = merge_stage(c, c->d_words[dst], 1, P.nkmers, &st);
   rc = finish(c, rc);
   if (rc == SHK_OK || st.chunks) {       // (the chunk is in the table: the stream has moved on, whatever a round behind it did)
-    F->cur ^= 1; F->state = end_state; F->tail_len = new_tail;
+    S->cur ^= 1; S->state = P.end_state; S->tail_len = P.new_tail;
   }
   if (stats) *stats = st;
-  if (fstats) { fstats->records = nrec; fstats->bases = nbases; fstats->breaks = nbreaks; fstats->kmers = st.kmers; }
+  if (fstats) { fstats->records = P.nrec; fstats->bases = P.nbases; fstats->breaks = P.nbreaks; fstats->kmers = st.kmers; }
   return rc;
+}
+
+// ------------------------------------------------------------------ FASTA text against the table (query_kernels.hip)
+extern "C" int shk_query_fasta(shk_ctx *c, const void *text, int text_on_device, uint64_t text_bytes, int first, uint32_t min_count,
+                               uint32_t *track, uint64_t track_cap, int track_on_device, shk_query_record *rec, uint32_t rec_cap, uint32_t *nrec,
+                               shk_query_stats *qstats) {
+  if (!c || (!text && text_bytes) || c->cfg.num_shards > 1 || !text_aligned(text, text_on_device)) return SHK_ERR_ARG;
+  if (c->front && c->front->count) return SHK_ERR_BATCH;     // (the call borrows the batch buffers their words may lie in)
+  if (text_bytes > c->cfg.max_batch_bytes) return SHK_ERR_BATCH;
+  HIPCHK(hipSetDevice(c->dev));
+  { int rc = table_sync(c); if (rc) return rc; }
+  if (upload_wait(c, text, text_on_device, c->stream)) return SHK_ERR_HIP;
+  { int rc = fasta_init(c); if (rc) return rc; }
+  ShkFasta *F = c->fasta;
+  ShkFasta::Stream *S = &F->s[FA_QUERY_STREAM];
+  ShkFaQuery Q;
+  Q.want_track = track != nullptr; Q.track_cap = track_cap; Q.want_rec = rec != nullptr; Q.rec_cap = rec_cap; Q.nrec_out = nrec;
+  ShkFaPiece P;
+  { int rc = fasta_front(c, S, text, text_on_device, text_bytes, first, &Q, &P); if (rc) return rc; }
+  const uint64_t nr = P.nrec + 1;
+  uint32_t *dtrack = nullptr;
+  if (track && P.nbases) {
+    dtrack = track;
+    if (!track_on_device) {
+      if (P.nbases > F->q_track_cap) {
+        hipFree(F->q_track); F->q_track = nullptr; F->q_track_cap = 0;
+        if (dmalloc(&F->q_track, P.nbases)) return finish(c, SHK_ERR_HIP);
+        F->q_track_cap = P.nbases;
+      }
+      dtrack = F->q_track;
+    }
+    HIPCHK(hipMemsetAsync(dtrack, 0xFF, P.nbases * 4, c->stream));
+  }
+  HIPCHK(hipMemsetAsync(F->q_rec, 0, nr * 32, c->stream));
+  if (P.nseg) {
+    ShkQueryArgs A;
+    A.rd_start = c->d_rd_start; A.rd_end = c->d_rd_end; A.pk_base = c->d_key_base; A.pk = (const ShkQuad *)c->d_words[1]; A.nseg = P.nseg;
+    A.k = c->cfg.k; A.hb = c->cfg.hb; A.tab = c->tab[c->cur]; A.q_lo = c->q_lo; A.nslots = c->nslots;
+    A.rec_start = F->q_rec + 4 * nr; A.nrec = P.nrec; A.tail = P.tail; A.min_count = min_count;
+    A.track = dtrack; A.track_len = P.nbases; A.acc = F->q_rec;
+    ProfScope ps(c, KP_ROLL_QUERY);
+    const uint32_t t = fasta_threads(c);
+    const uint64_t blocks = P.nseg / t + 1, most = c->threads < 512 ? 4 : 4096;      // (small workgroups: the CPU emulator build of the tests)
+    hipLaunchKernelGGL(k_roll_query, dim3((uint32_t)(blocks < most ? blocks : most)), dim3(t), 0, c->stream, A);
+  }
+  HIPCHK(hipGetLastError());
+  std::vector<shk_query_record> own;
+  shk_query_record *hr = rec;
+  if (!hr) { own.resize(nr); hr = own.data(); }
+  static_assert(sizeof(shk_query_record) == 32, "a record is the kernel's four sums");
+  HIPCHK(hipMemcpyAsync(hr, F->q_rec, nr * 32, hipMemcpyDeviceToHost, c->stream));
+  if (dtrack && !track_on_device) HIPCHK(hipMemcpyAsync(track, dtrack, P.nbases * 4, hipMemcpyDeviceToHost, c->stream));
+  const int rc = finish(c, SHK_OK);
+  if (rc) return rc;
+  shk_query_stats q = {P.nrec, P.nbases, P.nbreaks, 0, 0, 0, 0};
+  for (uint64_t i = 0; i < nr; i++) { q.kmers += hr[i].kmers; q.present += hr[i].present; q.solid += hr[i].solid; q.sum += hr[i].sum; }
+  if (q.kmers != P.nkmers) return SHK_ERR_CORRUPT;      // (every k-mer the segments hold has been answered, once)
+  S->cur ^= 1; S->state = P.end_state; S->tail_len = P.new_tail;
+  if (qstats) *qstats = q;
+  return SHK_OK;
 }
 
 // where routed words go: one of two alternating send buffers (allocated on first use)

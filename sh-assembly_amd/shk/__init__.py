@@ -13,6 +13,7 @@ LIB_PATH = os.path.join(os.path.dirname(_HERE), "libshk.so")
 
 MAX_CHUNKS = 4096
 FASTA_SEGMENT = 256           # SHK_FASTA_SEGMENT (include/shk.h)
+QUERY_NONE = 0xFFFFFFFF       # SHK_QUERY_NONE (include/shk.h): a track entry at which no k-mer ends
 
 
 class Config(C.Structure):
@@ -48,6 +49,15 @@ class SpectrumTotals(C.Structure):
 class FastaStats(C.Structure):
     """shk_fasta_stats (include/shk.h)"""
     _fields_ = [("records", C.c_uint64), ("bases", C.c_uint64), ("breaks", C.c_uint64), ("kmers", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class QueryStats(C.Structure):
+    """shk_query_stats (include/shk.h)"""
+    _fields_ = [("records", C.c_uint64), ("bases", C.c_uint64), ("breaks", C.c_uint64), ("kmers", C.c_uint64),
+                ("present", C.c_uint64), ("solid", C.c_uint64), ("sum", C.c_uint64)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -92,7 +102,7 @@ EXPORTS = ["shk_create", "shk_destroy", "shk_count_chunks", "shk_hash_chunks", "
            "shk_stats", "shk_header", "shk_export_blocks", "shk_export_cqf", "shk_import_cqf", "shk_import_blocks",
            "shk_lookup", "shk_profile_enable", "shk_profile_get", "shk_profile_reset", "shk_strerror",
            "shk_last_error_bits", "shk_insert_counted", "shk_dump", "shk_merge", "shk_multi_merge", "shk_import_shards", "shk_table_ptr", "shk_unitigs_add_reads",
-           "shk_spectrum", "shk_inner_product", "shk_magnitude", "shk_intersect", "shk_count_fasta", "shk_split_batches", "shk_sample_chunks"]
+           "shk_spectrum", "shk_inner_product", "shk_magnitude", "shk_intersect", "shk_count_fasta", "shk_split_batches", "shk_sample_chunks", "shk_query_fasta"]
 
 _libs = {}
 
@@ -112,6 +122,7 @@ def load(path=None):
     L.shk_destroy.restype = None
     L.shk_count_chunks.argtypes = [vp, vp, i32, u64, pu64, pu64, u32, C.POINTER(BatchStats)]
     L.shk_count_fasta.argtypes = [vp, vp, i32, u64, i32, C.POINTER(BatchStats), C.POINTER(FastaStats)]
+    L.shk_query_fasta.argtypes = [vp, vp, i32, u64, i32, u32, vp, u64, i32, vp, u32, C.POINTER(u32), C.POINTER(QueryStats)]
     L.shk_sample_chunks.argtypes = [vp, vp, i32, u64, pu64, pu64, u32, u32, C.POINTER(BatchStats), C.POINTER(SampleStats)]
     L.shk_hash_chunks.argtypes = [vp, vp, i32, u64, pu64, pu64, u32, C.POINTER(vp), pu64]
     L.shk_upload_text.argtypes = [vp, vp, u64, C.POINTER(vp)]
@@ -278,6 +289,31 @@ class Context:
             ptr, n = C.cast(buf, C.c_void_p), len(text)
         self._chk(self.L.shk_count_fasta(self.h, ptr, 1 if on_device else 0, n, 1 if first else 0, C.byref(st), C.byref(fs)))
         return st.as_dict(), fs.as_dict()
+
+    def query_fasta(self, text, first=True, min_count=2, want_track=False, on_device=False, text_bytes=None):
+        """one piece of a FASTA query stream against the table (shk_query_fasta); text as in count_fasta. Returns (statistics
+        dict, the piece's records as an (n, 4) uint64 array of kmers / present / solid / sum -- row 0 continues the record
+        that was open when the piece began --, the track as a uint32 array with one entry per base of the piece, or None)."""
+        import numpy as np
+        if on_device or isinstance(text, int):
+            ptr, n = C.c_void_p(int(text)), int(text_bytes)
+        else:
+            buf = (C.c_char * max(len(text), 1)).from_buffer_copy(bytes(text) or b"\0")
+            ptr, n = C.cast(buf, C.c_void_p), len(text)
+        track = np.empty(max(n, 1), dtype=np.uint32) if want_track else None      # (a piece of n bytes has at most n bases)
+        nrec, qs = C.c_uint32(), QueryStats()
+        cap = 1024
+        while True:
+            rec = np.zeros((cap, 4), dtype=np.uint64)
+            rc = self.L.shk_query_fasta(self.h, ptr, 1 if on_device else 0, n, 1 if first else 0, int(min_count),
+                                        C.c_void_p(track.ctypes.data) if want_track else None, n if want_track else 0, 0,
+                                        C.c_void_p(rec.ctypes.data), cap, C.byref(nrec), C.byref(qs))
+            if rc == -7 and nrec.value > cap:      # more records than that: the call says how many, and has moved nothing
+                cap = nrec.value
+                continue
+            self._chk(rc)
+            break
+        return qs.as_dict(), rec[:nrec.value].copy(), (track[:qs.bases].copy() if want_track else None)
 
     def sample_chunks(self, text, chunk_off, chunk_len, sample_bits, on_device=False, text_bytes=None):
         """count the k-mers whose canonical hash has bits [hb, hb + sample_bits) zero (shk_sample_chunks); text as in
