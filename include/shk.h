@@ -550,6 +550,10 @@ uint32_t shk_last_error_bits(shk_ctx *ctx);
  * key instead of 8, between the roll kernels and the middle level of a three-level context that owns the whole filter;
  * SHK_RP_SPLIT=0, read by shk_create, keeps every batch on 8-byte words). The profile's kernel names do not tell. */
 uint64_t shk_split_batches(shk_ctx *ctx);
+/* diagnostics: launches of the record-sourced rebuild kernels since shk_create that loaded every region's old record and
+ * first words up front. They do so when the batch in hand brings eight words per region or more; SHK_MERGE_PREFETCH=0, read
+ * by shk_create, keeps every launch on the dependent loads. The results are the same either way. */
+uint64_t shk_prefetch_passes(shk_ctx *ctx);
 
 #ifdef __cplusplus
 }

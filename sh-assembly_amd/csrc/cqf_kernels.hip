@@ -71,6 +71,8 @@ struct ShkMergeArgs {
   uint32_t rstride;               // region = (blockIdx.x + r0) * rstride: > 1 for the statistics pass over a sample of the regions
   int counted;                    // 1: the records' chunk field holds (multiplicity - 1) of a counted insert (insert_advance with
                                   // count > 1, gqf.c:2024-2136); every record takes part, no chunk statistics
+  uint32_t prefetch;              // 1 = a dense pass (the host's gate, fill_args): a record-sourced launch takes the instantiation that
+                                  // loads a region's old record and first round of words before anything is known about the region
 };
 
 __device__ __forceinline__ unsigned shk_img_slot_off(unsigned p) {
@@ -248,8 +250,10 @@ __device__ __forceinline__ uint32_t shk_fold_home(uint32_t tag) { return (__umul
 // image, no rank/select: a lane's four length bytes say which of its quotients have a run, a wave sum of the lanes' byte
 // totals where its first run starts. Not for the write pass, nor for a deNoise round: that one reads the protection
 // marks k_denoise_marks has just put into table A's traveled words (its own marks only -- a reader's are zeroed first).
-template <int MODE, int IMGB, bool FUSED = false, bool OLDREC = false>
+// PF: the early loads of a dense pass (below); the host picks the instantiation by its gate, ShkMergeArgs::prefetch.
+template <int MODE, int IMGB, bool FUSED = false, bool OLDREC = false, bool PF = false>
 __global__ void __launch_bounds__(SHK_MERGE_GROUP) k_region_merge(ShkMergeArgs A) {
+  static_assert(!PF || (OLDREC && SHK_MERGE_GROUP == 2 * SHK_WAVE), "the early loads read a record, one packed dword per lane of two waves");
   static_assert(!FUSED || MODE == 3, "the one-pass deNoise point is a spill-mode pass");
   static_assert(!OLDREC || MODE == 0 || MODE == 3, "the write pass reads the table");
   constexpr bool WRITE = MODE == 1;                // builds the image and stores table B
@@ -293,6 +297,47 @@ __global__ void __launch_bounds__(SHK_MERGE_GROUP) k_region_merge(ShkMergeArgs A
   const unsigned ngrp = blockDim.x;              // all waves of the group: staging, init, key folding
   constexpr unsigned nthr = SHK_MERGE_THREADS;   // one wave does the rest
   const uint32_t r = A.list ? A.list[blockIdx.x] : (blockIdx.x + A.r0) * A.rstride;
+  // A dense pass (PF) issues all of the region's loads here, before it knows anything about the region. None of their
+  // addresses depends on loaded data, so they are all on their way at once, together with the region's extents in the old
+  // table, and the LDS init runs meanwhile: one wait where the kernel otherwise waits four times in a row (the region's
+  // extents, its record's lengths, as many packed bytes as they add up to, and behind the barrier its words).
+  // - The record lies at A.orec + r * SHK_SPILL_STRIDE and is SHK_SPILL_STRIDE valid bytes whatever it holds: the first
+  //   wave takes the length dwords, the two waves one dword each of the packed part, all of it.
+  // - With a slotted last level the region's words start at r * region_cap. The lane's four words of the first round are
+  //   loaded at the indices below region_cap: they never leave the region's own slot, and the buffer holds
+  //   nregions * region_cap records (partition_stage: region_cap <= 2 * max_batch_keys / nregions, two 4-byte records to
+  //   each of its max_batch_keys + 1 words) whether the slot is full or not. Which of them count is decided below by
+  //   the region's end offset, as for words loaded there. Unslotted words and later rounds keep the dependent load.
+  //   The region's end offset in the words is asked for with them.
+  // An empty region leaves as before and drops what was loaded: the host takes this instantiation only for a pass in
+  // which hardly any region is empty (fill_args).
+  constexpr bool pf = PF;
+  const bool pfw = pf && A.words && A.region_cap;
+  uint32_t pf_l4 = 0, pf_pk = 0, pf_w[4] = {~0u, ~0u, ~0u, ~0u};
+  uint64_t pf_end = 0;            // pfw: A.region_base[r], the end of the region's slot
+  // (16-byte LDS stores: the LDS pipeline, shared by all waves of the CU, is what this kernel keeps busiest)
+  auto lds_init = [&]() {
+    const uint4 e4 = make_uint4(SHK_EMPTY, SHK_EMPTY, SHK_EMPTY, SHK_EMPTY), z4 = make_uint4(0, 0, 0, 0);
+    for (uint32_t i = tid; i < SHK_HCAP / 4; i += ngrp) reinterpret_cast<uint4 *>(hkey)[i] = e4;
+    for (uint32_t i = tid; i < SHK_HCAP / 4; i += ngrp) reinterpret_cast<uint4 *>(hcnt)[i] = z4;
+    for (uint32_t i = tid; i < SHK_REGION / 8; i += ngrp) reinterpret_cast<uint4 *>(qcnt)[i] = z4;
+    if (tid < 2 * SHK_WAVE) hidle[tid] = 0;
+  };
+  if (pf) {
+    static_assert(SHK_SPILL_PACK_MAX / 4 == 2 * SHK_WAVE, "one packed dword per lane of the two waves");
+    const uint32_t *src = reinterpret_cast<const uint32_t *>(A.orec + (size_t)r * SHK_SPILL_STRIDE);
+    if (tid < SHK_WAVE) pf_l4 = src[tid];
+    pf_pk = src[SHK_SPILL_LENS / 4 + tid];
+    if (pfw) {
+      const uint32_t *wp0 = A.words + (uint64_t)r * A.region_cap;
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        const uint32_t i = (uint32_t)u * (2 * SHK_WAVE) + tid;
+        if (i < A.region_cap) pf_w[u] = wp0[i];
+      }
+      pf_end = A.region_base[r];
+    }
+  }
   const uint32_t nregions = (uint32_t)((A.nslots + SHK_REGION - 1) / SHK_REGION);
   const uint64_t q0 = (uint64_t)r * SHK_REGION;
   const uint32_t nq = (uint32_t)((A.nslots - q0) < SHK_REGION ? (A.nslots - q0) : SHK_REGION);
@@ -301,6 +346,7 @@ __global__ void __launch_bounds__(SHK_MERGE_GROUP) k_region_merge(ShkMergeArgs A
 
   // ---- old extent of this region in table A
   const uint64_t fa0 = A.finA[r], fa1 = A.finA[r + 1];
+  if (pf) lds_init();   // (in front of the first use of anything loaded)
   const uint64_t olo_abs = fa0 > q0 ? fa0 : q0;
   const bool old_any = fa1 > olo_abs;
   const uint32_t olo = (uint32_t)(olo_abs - q0);
@@ -320,7 +366,7 @@ __global__ void __launch_bounds__(SHK_MERGE_GROUP) k_region_merge(ShkMergeArgs A
 
   // A region without old runs and without words has nothing to say: T = 0, no statistics, all lengths 0
   // (sparse tables -- the first batches of a build, big filters -- are mostly such regions)
-  if ((MODE == 0 || MODE == 3) && !old_any && !fatal && (!A.words || (A.region_cap ? A.region_base[r] == (uint64_t)r * A.region_cap : A.region_base[r] == A.region_base[r + 1]))) {
+  if ((MODE == 0 || MODE == 3) && !old_any && !fatal && (!A.words || (A.region_cap ? (pfw ? pf_end : A.region_base[r]) == (uint64_t)r * A.region_cap : A.region_base[r] == A.region_base[r + 1]))) {
     if (tid < SHK_SUM_STRIDE) A.summary[(size_t)SHK_SUM_STRIDE * r + tid] = 0;
     if (MODE == 3 && tid < SHK_WAVE) reinterpret_cast<uint32_t *>(A.spill + (size_t)r * SHK_SPILL_STRIDE)[tid] = 0;
     if (FUSED) {
@@ -336,7 +382,19 @@ __global__ void __launch_bounds__(SHK_MERGE_GROUP) k_region_merge(ShkMergeArgs A
   {
     if (OLDREC) {
       // the first wave, which goes on to merge, keeps its length bytes and copies as many packed bytes as they add up to
-      if (tid < SHK_WAVE) {
+      if (pf) {
+        // loaded above: every lane of the two waves stores its packed dword (the bytes behind the runs' total are never
+        // read), the first wave keeps its length bytes
+        if (tid < SHK_WAVE) {
+          ol4 = pf_l4;
+          const uint32_t mine = (ol4 & 255u) + ((ol4 >> 8) & 255u) + ((ol4 >> 16) & 255u) + (ol4 >> 24);
+          const uint32_t sincl = shk_wave_incl_add(mine);
+          oex = sincl - mine;
+          const uint32_t ototal = (uint32_t)__builtin_amdgcn_readlane((int)sincl, SHK_WAVE - 1);
+          if (ototal > SHK_SPILL_PACK_MAX) { orec_bad = true; ol4 = 0; }   // (not a record this library wrote)
+        }
+        reinterpret_cast<uint32_t *>(opk)[tid] = pf_pk;
+      } else if (tid < SHK_WAVE) {
         const uint32_t *src = reinterpret_cast<const uint32_t *>(A.orec + (size_t)r * SHK_SPILL_STRIDE);
         ol4 = src[tid];
         const uint32_t mine = (ol4 & 255u) + ((ol4 >> 8) & 255u) + ((ol4 >> 16) & 255u) + (ol4 >> 24);
@@ -353,14 +411,7 @@ __global__ void __launch_bounds__(SHK_MERGE_GROUP) k_region_merge(ShkMergeArgs A
     uint32_t *dst = reinterpret_cast<uint32_t *>(oimg);
     if (!(A.ablate & 64)) for (uint32_t i = tid; i < (nbytes + 3) / 4; i += ngrp) dst[i] = src[i];
     }
-    // (16-byte LDS stores: the LDS pipeline, shared by all waves of the CU, is what this kernel keeps busiest)
-    {
-      const uint4 e4 = make_uint4(SHK_EMPTY, SHK_EMPTY, SHK_EMPTY, SHK_EMPTY), z4 = make_uint4(0, 0, 0, 0);
-      for (uint32_t i = tid; i < SHK_HCAP / 4; i += ngrp) reinterpret_cast<uint4 *>(hkey)[i] = e4;
-      for (uint32_t i = tid; i < SHK_HCAP / 4; i += ngrp) reinterpret_cast<uint4 *>(hcnt)[i] = z4;
-      for (uint32_t i = tid; i < SHK_REGION / 8; i += ngrp) reinterpret_cast<uint4 *>(qcnt)[i] = z4;
-    }
-    if (tid < 2 * SHK_WAVE) hidle[tid] = 0;
+    if (!pf) lds_init();
     if (WRITE) {
       uint32_t *z = reinterpret_cast<uint32_t *>(nimg);
       for (uint32_t i = tid; i < (IMG_BYTES + 16) / 4; i += ngrp) z[i] = 0;
@@ -380,7 +431,7 @@ __global__ void __launch_bounds__(SHK_MERGE_GROUP) k_region_merge(ShkMergeArgs A
   // not the few lanes whose word `u` happens to be the collided one. Loop conditions are wave-uniform.
   uint32_t my_added = 0, my_added_b = 0;
   if (A.words && !fatal && !(A.ablate & 1)) {
-    const uint64_t kb = A.region_cap ? (uint64_t)r * A.region_cap : A.region_base[r], ke = A.region_cap ? A.region_base[r] : A.region_base[r + 1];
+    const uint64_t kb = A.region_cap ? (uint64_t)r * A.region_cap : A.region_base[r], ke = A.region_cap ? (pfw ? pf_end : A.region_base[r]) : A.region_base[r + 1];
     const unsigned lane = shk_lane();
     const bool wh = A.want_hist != 0;
     bool corrupt = false, hfull = false;
@@ -408,10 +459,15 @@ __global__ void __launch_bounds__(SHK_MERGE_GROUP) k_region_merge(ShkMergeArgs A
     };
     for (uint32_t i0 = 0; i0 < nw; i0 += 4 * ngrp) {
       uint32_t wv[4];
+      if (pfw && i0 == 0) {           // (the first round's words were loaded at the top)
 #pragma unroll
-      for (int u = 0; u < 4; u++) {
-        const uint32_t i = i0 + (uint32_t)u * ngrp + tid;
-        wv[u] = i < nw ? wp[i] : ~0u;
+        for (int u = 0; u < 4; u++) wv[u] = (uint32_t)u * ngrp + tid < nw ? pf_w[u] : ~0u;
+      } else {
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+          const uint32_t i = i0 + (uint32_t)u * ngrp + tid;
+          wv[u] = i < nw ? wp[i] : ~0u;
+        }
       }
       uint32_t q[4], qh[4];   // the lane's words (QPEND = to be counted) and the entry each probes next
 #pragma unroll

@@ -204,6 +204,11 @@ struct shk_ctx : ShkStageBufs {
   int prof_on;                  // profiling: kernel times are recorded (ShkStageBufs::prof_ms)
   double new_frac;              // new distinct keys per presented k-mer in the last committed range (predicts crossings)
   int staged;                   // which d_words[] holds the partitioned words of shk_stage_words
+  // The record-sourced rebuild kernels load a region's old record and its first words before they know whether the region
+  // has any (ShkMergeArgs::prefetch): right for a dense pass, wasted bytes where most regions are empty and leave at once.
+  uint64_t pass_words;          // words of the partitioned batch in hand (merge_stage, shk_stage_words*)
+  int prefetch_ok;              // 0: never (SHK_MERGE_PREFETCH=0)
+  uint64_t prefetch_passes;     // launches that ran with the early loads (shk_prefetch_passes)
   // one-pass deNoise point (denoise_fused): the intermediate table's (T, c), run lengths and free pointers; protected quotients
   uint32_t *d_isum; uint8_t *d_ilens; uint64_t *d_fin_i; uint64_t *d_prot;
   int counted;                  // 1 while shk_insert_counted runs: the words' chunk field is a multiplicity
@@ -458,6 +463,7 @@ static int create_init(shk_ctx *c, const shk_config *cfg) {
   c->lazy_ok = 1;
   c->foreign_marks = 0;
   if (const char *e = getenv("SHK_LAZY_PLACE")) c->lazy_ok = atoi(e) != 0;
+  c->prefetch_ok = !(getenv("SHK_MERGE_PREFETCH") && atoi(getenv("SHK_MERGE_PREFETCH")) == 0);
   if (dmalloc(&c->spill[0], (uint64_t)c->nregions * SHK_SPILL_STRIDE) || dmalloc(&c->d_over_list, (uint64_t)c->nregions + 1)) return SHK_ERR_HIP;
   { uint64_t nt = c->nregions / SHK_RSCAN_TILE + 2;
     if (dmalloc(&c->d_tile_a, nt) || dmalloc(&c->d_tile_b, nt) || dmalloc(&c->d_tile_f, nt)) return SHK_ERR_HIP; }
@@ -1015,9 +1021,11 @@ static void launch_merge(shk_ctx *c, const ShkMergeArgs &A0, bool rec = false) {
   SHK_FOR_REGION_SLICES(c, A, nblk) {
     // (the write pass, MODE 1, has no record-sourced form: naming MODE 0 in its place keeps launch_merge<1> from
     // instantiating one that the test in front never lets run)
-    if (MODE != 1 && rec)
-      hipLaunchKernelGGL((k_region_merge<MODE == 1 ? 0 : MODE, SHK_IMG_BLOCKS, false, true>), dim3(nblk), dim3(SHK_MERGE_GROUP), 0, c->stream, A);
-    else if (c->big_image)
+    if (MODE != 1 && rec) {
+      c->prefetch_passes += A.prefetch;
+      if (A.prefetch) hipLaunchKernelGGL((k_region_merge<MODE == 1 ? 0 : MODE, SHK_IMG_BLOCKS, false, true, true>), dim3(nblk), dim3(SHK_MERGE_GROUP), 0, c->stream, A);
+      else hipLaunchKernelGGL((k_region_merge<MODE == 1 ? 0 : MODE, SHK_IMG_BLOCKS, false, true>), dim3(nblk), dim3(SHK_MERGE_GROUP), 0, c->stream, A);
+    } else if (c->big_image)
       hipLaunchKernelGGL((k_region_merge<MODE, SHK_IMG_BLOCKS_BIG>), dim3(nblk), dim3(SHK_MERGE_GROUP), 0, c->stream, A);
     else
       hipLaunchKernelGGL((k_region_merge<MODE, SHK_IMG_BLOCKS>), dim3(nblk), dim3(SHK_MERGE_GROUP), 0, c->stream, A);
@@ -1083,6 +1091,9 @@ static void fill_args(shk_ctx *c, ShkMergeArgs *A, const uint64_t *words, uint32
   A->spill = spill_out(c); A->orec = c->spill[c->live]; A->over_list = c->d_over_list; A->n_over = c->d_counters + SHK_CNT_NOVER; A->list = nullptr;
   A->newchunks = nullptr; A->chist = nullptr;
   A->counted = c->counted;
+  // the early loads: the records are live (a record-sourced launch) and the batch brings eight words per region or more --
+  // regions are hash buckets, so fewer than 0.04 % of them are empty then (e^-8)
+  A->prefetch = c->prefetch_ok && c->rec_live && words && c->pass_words >= 8ULL * c->nregions;
   A->r0 = 0; A->rstride = 1;
   A->split = ~0u; A->isum = nullptr; A->ilens = nullptr; A->prot_list = nullptr; A->nprot = 0;
   A->summary = c->d_summary; A->counters = c->d_counters; A->err = c->d_err;
@@ -1319,7 +1330,9 @@ static int point_try(shk_ctx *c, const uint64_t *words, uint32_t lo, uint32_t sp
   HIPCHK(hipMemsetAsync(c->d_counters, 0, SHK_NCOUNTERS * 8, c->stream));
   { ProfScope ps(c, KP_MERGE_FUSED);
     SHK_FOR_REGION_SLICES(c, A, nblk) {
-      if (c->rec_live) hipLaunchKernelGGL((k_region_merge<3, SHK_IMG_BLOCKS, true, true>), dim3(nblk), dim3(SHK_MERGE_GROUP), 0, c->stream, A);
+      if (c->rec_live) c->prefetch_passes += A.prefetch;
+      if (c->rec_live && A.prefetch) hipLaunchKernelGGL((k_region_merge<3, SHK_IMG_BLOCKS, true, true, true>), dim3(nblk), dim3(SHK_MERGE_GROUP), 0, c->stream, A);
+      else if (c->rec_live) hipLaunchKernelGGL((k_region_merge<3, SHK_IMG_BLOCKS, true, true>), dim3(nblk), dim3(SHK_MERGE_GROUP), 0, c->stream, A);
       else hipLaunchKernelGGL((k_region_merge<3, SHK_IMG_BLOCKS, true>), dim3(nblk), dim3(SHK_MERGE_GROUP), 0, c->stream, A);
     } }
   point_scans(c, true, true, 0);
@@ -1378,7 +1391,9 @@ static int point_finish(shk_ctx *c, const uint64_t *words, uint32_t lo, uint32_t
     HIPCHK(hipMemcpyAsync(c->d_over_list, regs.data(), regs.size() * 4, hipMemcpyHostToDevice, c->stream));
     A.list = c->d_over_list; A.prot_list = c->d_prot; A.nprot = (uint32_t)nprot;
     { ProfScope ps(c, KP_MISC);   // (the same old side as the first go: its records are untouched)
-      if (c->rec_live) hipLaunchKernelGGL((k_region_merge<3, SHK_IMG_BLOCKS, true, true>), dim3((uint32_t)regs.size()), dim3(SHK_MERGE_GROUP), 0, c->stream, A);
+      if (c->rec_live) c->prefetch_passes += A.prefetch;
+      if (c->rec_live && A.prefetch) hipLaunchKernelGGL((k_region_merge<3, SHK_IMG_BLOCKS, true, true, true>), dim3((uint32_t)regs.size()), dim3(SHK_MERGE_GROUP), 0, c->stream, A);
+      else if (c->rec_live) hipLaunchKernelGGL((k_region_merge<3, SHK_IMG_BLOCKS, true, true>), dim3((uint32_t)regs.size()), dim3(SHK_MERGE_GROUP), 0, c->stream, A);
       else hipLaunchKernelGGL((k_region_merge<3, SHK_IMG_BLOCKS, true>), dim3((uint32_t)regs.size()), dim3(SHK_MERGE_GROUP), 0, c->stream, A); }
     HIPCHK(hipStreamSynchronize(c->stream));   // (regs lives on this stack frame)
     point_scans(c, true, false, 0);
@@ -1484,7 +1499,9 @@ static int sample_pass(shk_ctx *c, const uint64_t *words, uint32_t lo, uint32_t 
     for (uint32_t r0 = 0; r0 < ns; r0 += SHK_REGION_SLICE) {
       A.r0 = r0;
       const uint32_t nblk = ns - r0 < SHK_REGION_SLICE ? ns - r0 : SHK_REGION_SLICE;
-      if (c->rec_live) hipLaunchKernelGGL((k_region_merge<0, SHK_IMG_BLOCKS, false, true>), dim3(nblk), dim3(SHK_MERGE_GROUP), 0, c->stream, A);
+      if (c->rec_live) c->prefetch_passes += A.prefetch;
+      if (c->rec_live && A.prefetch) hipLaunchKernelGGL((k_region_merge<0, SHK_IMG_BLOCKS, false, true, true>), dim3(nblk), dim3(SHK_MERGE_GROUP), 0, c->stream, A);
+      else if (c->rec_live) hipLaunchKernelGGL((k_region_merge<0, SHK_IMG_BLOCKS, false, true>), dim3(nblk), dim3(SHK_MERGE_GROUP), 0, c->stream, A);
       else hipLaunchKernelGGL((k_region_merge<0, SHK_IMG_BLOCKS>), dim3(nblk), dim3(SHK_MERGE_GROUP), 0, c->stream, A);
     }
     hipLaunchKernelGGL(k_chunk_hist, dim3((ns + SHK_CHIST_REGIONS - 1) / SHK_CHIST_REGIONS), dim3(256), 0, c->stream,
@@ -1646,6 +1663,7 @@ static int merge_stage_from(shk_ctx *c, const uint64_t *words, uint32_t nchunks,
 // thins the table out again).
 static int merge_stage(shk_ctx *c, const uint64_t *words, uint32_t nchunks, uint64_t nwords, shk_batch_stats *st) {
   uint32_t lo = 0;
+  c->pass_words = nwords;
   int rc = merge_stage_from(c, words, nchunks, nwords, st, &lo);
   if (rc == SHK_ERR_REGION && !c->big_image && (c->last_err_bits & (SHK_E_OLD_EXTENT | SHK_E_NEW_EXTENT))) {
     c->big_image = 1;
@@ -2409,7 +2427,7 @@ extern "C" int shk_stage_words_pair(shk_ctx *c, const uint64_t *d_a, uint64_t na
   HIPCHK(hipMemcpyAsync(c->d_scalars + DS_PAIR_LEN, c->h_pinned + HP_PAIR, sizeof(pair), hipMemcpyHostToDevice, c->stream));
   int dst = 0;
   int rc = partition_stage(c, c, part_from_words(c, d_a, na, d_b, nb), &dst);
-  c->staged = dst;
+  c->staged = dst; c->pass_words = na + nb;
   return finish(c, rc);
 }
 
@@ -2419,7 +2437,7 @@ extern "C" int shk_stage_words(shk_ctx *c, const uint64_t *d_words, uint64_t nwo
   HIPCHK(hipSetDevice(c->dev));
   int dst = 0;
   int rc = partition_words(c, d_words, nwords, &dst);
-  c->staged = dst;
+  c->staged = dst; c->pass_words = nwords;
   return finish(c, rc);
 }
 
@@ -2789,6 +2807,7 @@ extern "C" int shk_insert_counted(shk_ctx *c, const uint64_t *keys, const uint64
         int dst = 0;
         rc = partition_stage(c, c, part_from_words(c, c->d_words[0], nwords), &dst);
         if (rc) break;
+        c->pass_words = nwords;
         MergeOut o;
         rc = merge_plain(c, c->d_words[dst], &o);
         if (rc) break;
@@ -3709,6 +3728,7 @@ extern "C" int shk_find_unitigs(shk_ctx *c, const char *seeds, const uint32_t *s
 }
 
 // batches whose first-level output took the split record (either front end), since the context was created
+extern "C" uint64_t shk_prefetch_passes(shk_ctx *c) { return c ? c->prefetch_passes : 0; }
 extern "C" uint64_t shk_split_batches(shk_ctx *c) { return c ? c->split_batches + (c->front ? c->front->b.split_batches : 0) : 0; }
 extern "C" int shk_profile_enable(shk_ctx *c, int on) { if (!c) return SHK_ERR_ARG; c->prof_on = on; return SHK_OK; }
 extern "C" int shk_profile_reset(shk_ctx *c) {

@@ -102,7 +102,8 @@ EXPORTS = ["shk_create", "shk_destroy", "shk_count_chunks", "shk_hash_chunks", "
            "shk_stats", "shk_header", "shk_export_blocks", "shk_export_cqf", "shk_import_cqf", "shk_import_blocks",
            "shk_lookup", "shk_profile_enable", "shk_profile_get", "shk_profile_reset", "shk_strerror",
            "shk_last_error_bits", "shk_insert_counted", "shk_dump", "shk_merge", "shk_multi_merge", "shk_import_shards", "shk_table_ptr", "shk_unitigs_add_reads",
-           "shk_spectrum", "shk_inner_product", "shk_magnitude", "shk_intersect", "shk_count_fasta", "shk_split_batches", "shk_sample_chunks", "shk_query_fasta"]
+           "shk_spectrum", "shk_inner_product", "shk_magnitude", "shk_intersect", "shk_count_fasta", "shk_split_batches", "shk_sample_chunks", "shk_query_fasta",
+           "shk_prefetch_passes"]
 
 _libs = {}
 
@@ -172,6 +173,8 @@ def load(path=None):
     L.shk_last_error_bits.restype = u32
     L.shk_split_batches.argtypes = [vp]
     L.shk_split_batches.restype = u64
+    L.shk_prefetch_passes.argtypes = [vp]
+    L.shk_prefetch_passes.restype = u64
     _libs[path] = L
     return L
 
@@ -650,3 +653,7 @@ class Context:
     def split_batches(self):
         """batches since creation whose first-level output took the split record (include/shk.h)"""
         return int(self.L.shk_split_batches(self.h))
+
+    def prefetch_passes(self):
+        """rebuild launches since creation that loaded the regions' records and first words up front (include/shk.h)"""
+        return int(self.L.shk_prefetch_passes(self.h))
