@@ -35,6 +35,8 @@
  *   shk_count_fasta       (no counterpart: the reference reads 4-line FASTQ only, cqf/CQF_mt.h:610-731) FASTA text of any shape
  *   shk_query_fasta       (no counterpart: the reference answers one hashed key at a time, qf_count_key_value) FASTA text against
  *                         the table: per-base counts and per-record totals
+ *   shk_query_reads       (no counterpart: the reference answers one hashed key at a time, qf_count_key_value) FASTQ reads
+ *                         against the table: per-read k-mer statistics, median count, per-window counts
  *   shk_sample_chunks     (no counterpart: the reference's README sends the user to ntCard) -N -n -e from the reads themselves
  *   shk_import_shards     (no counterpart: the reference is one process) quotient-range shards -> the single table
  *   shk_stats             runtime->nelts / ndistinct_elts / num_deNoise    cqf/CQF_mt.h:277-288
@@ -243,6 +245,59 @@ int shk_query_fasta(shk_ctx *ctx, const void *text, int text_on_device, uint64_t
                     uint32_t *track, uint64_t track_cap, int track_on_device,      /* track may be NULL */
                     shk_query_record *rec, uint32_t rec_cap, uint32_t *nrec,       /* rec may be NULL; host memory */
                     shk_query_stats *qstats /* may be NULL */);
+
+/* ---- FASTQ reads against the table (no counterpart in the reference): what does the table know about every read? Per read
+ * the number of its k-mers, how many of them the table holds, their smallest, largest and median count, and optionally
+ * every window's count; the table stays untouched. The job of a decontamination or baiting filter, of abundance
+ * filtering by median count, of haplotype binning against two parental tables (one call each).
+ *   - Text and chunks: exactly shk_count_chunks' contract (host text, or device text aligned to 16 bytes; 1 .. 4096 chunks
+ *     in any order, with gaps, empty or shorter than 16 bytes; lines counted from each chunk's first byte). The reads are
+ *     the ones the FASTQ front end finds, in its order: chunk by chunk in the order of the call, text order inside a chunk.
+ *     *nreads = their number.
+ *   - ext (may be NULL; host memory, rec_cap entries): ext[r] = read r's sequence line as the front end hands it over:
+ *     seq_off = the offset of its first byte in `text`, seq_len = its length up to, not including, the line feed (a '\r' in
+ *     front of the line feed belongs to it), chunk = the index of its chunk in the call.
+ *   - Which k-mers: window j of a read is bytes [j, j + k) of its sequence line, and a window is a k-mer exactly when all k
+ *     bytes are one of A C G T a c g t -- shk_query_fasta's rule, so a read answers the same whether asked as FASTQ or as
+ *     a two-line FASTA record. Its key is the one the counting paths give that k-mer: canonical ntHash masked to hb bits.
+ *     A window that holds any other byte (N, the IUPAC codes, '\r', anything) is no k-mer. This is deliberately NOT the
+ *     stream of reads_to_kmers, which hashes the first window of a read and the window behind an 'N' without looking at
+ *     them (shk_count_chunks restates that; see shk_count_fasta's comment): for reads made of bases only the two agree.
+ *     A read shorter than k has no k-mers. 1 <= k <= 191, every geometry.
+ *   - rec[r], over the counts c of read r's k-mers: kmers = their number, present = those with c >= 1, solid = those with
+ *     c >= min_count, sum = the true counts added up mod 2^64; min, max and median over the counts capped at 0xFFFFFFFE,
+ *     absent k-mers (count 0) included. median is the LOWER median, sorted[(kmers - 1) / 2] -- an integer, unlike the
+ *     averaging median of shk_unitigs_from_seeds -- and is computed only with SHK_READS_MEDIAN in flags; without it the
+ *     field is SHK_QUERY_NONE. A read without k-mers has min = max = 0 (and median 0 when asked for). rec is host memory
+ *     unless rec_on_device != 0.
+ *   - track (may be NULL; a host pointer unless track_on_device != 0): entry woff[r] + j belongs to window j of read r,
+ *     woff[r] = the sum over earlier reads of max(seq_len - k + 1, 0). Its value is the capped count, or SHK_QUERY_NONE
+ *     where the window is no k-mer. *nwindows = the number of windows of the call. With track == NULL and no median
+ *     asked for the call writes nothing per window.
+ *   - rstats (may be NULL): reads, and the sums of kmers, present, solid and sum over the call.
+ *   - It is a reader: it launches the pending lazy placement first, as shk_lookup does, reads with mark mode 2 (traveled
+ *     bits are neither read nor set), and changes no byte of the table and no runtime counter.
+ * Errors: nothing is written to rec, ext or track, and the table is untouched. SHK_ERR_ARG for a sharded context, device
+ * text that is not 16-byte aligned, NULL rec, nreads or chunk arrays, unknown flag bits; SHK_ERR_BATCH for nchunks outside
+ * 1 .. 4096, text, reads or windows beyond the context's capacities (windows are bounded by max_batch_keys: the per-window
+ * scratch is borrowed from the key-word buffers), batches prepared and not yet counted, track_cap < *nwindows, or rec_cap
+ * < *nreads -- *nreads and *nwindows are then still set to what is needed, so the call can be repeated; SHK_ERR_FASTQ
+ * for a read of more than 65535 bases.
+ * Besides the batch buffers it borrows (the text buffer, the read arrays, the two key-word buffers: 2-bit units in one,
+ * the per-window values of a call with a median or a host track in the other), a context that has answered such a query
+ * keeps 44 bytes per read of max_batch_reads: the windows of every read and their offsets (pack_stage owns the front
+ * end's own pair of arrays for the units' flags and places) and the records of a call whose rec is host memory. */
+#define SHK_READS_MEDIAN 1u
+typedef struct shk_read_record { uint64_t sum; uint32_t kmers, present, solid, min, median, max; } shk_read_record;   /* 32 bytes */
+typedef struct shk_read_extent { uint64_t seq_off; uint32_t seq_len, chunk; } shk_read_extent;                        /* 16 bytes */
+typedef struct shk_reads_stats { uint64_t reads, kmers, present, solid, sum; } shk_reads_stats;
+int shk_query_reads(shk_ctx *ctx, const void *text, int text_on_device, uint64_t text_bytes,
+                    const uint64_t *chunk_off, const uint64_t *chunk_len, uint32_t nchunks,
+                    uint32_t min_count, uint32_t flags,
+                    shk_read_record *rec, uint64_t rec_cap, int rec_on_device, uint64_t *nreads,
+                    shk_read_extent *ext,                                   /* may be NULL; host memory, rec_cap entries */
+                    uint32_t *track, uint64_t track_cap, int track_on_device, uint64_t *nwindows,   /* track may be NULL */
+                    shk_reads_stats *rstats /* may be NULL */);
 
 /* ---- a hash-sampled spectrum of the reads (no counterpart in the reference, whose README sends the user to ntCard for
  * the -N -n -e its command line wants). Hashes every k-mer of the FASTQ chunks exactly as shk_count_chunks does (the

@@ -25,17 +25,18 @@
 #include "unitig_kernels.hip"
 #include "fasta_kernels.hip"
 #include "query_kernels.hip"
+#include "reads_kernels.hip"
 
 #define SHK_SLACK 256  // bytes of slack behind buffers read with wide loads
 
 enum {
   KP_COUNT_LINES, KP_SCAN_CHUNKS, KP_EMIT_READS, KP_COUNT_KEYS, KP_HASH, KP_SCAN, KP_RP_PREP, KP_RP_HIST,
-  KP_RP_SCATTER, KP_MERGE_SUM, KP_REGION_SCAN, KP_MERGE_WRITE, KP_MERGE_SPILL, KP_PLACE, KP_MARKS, KP_LOOKUP, KP_WALK, KP_UG_WALK, KP_UG_FINISH, KP_MERGE_FUSED, KP_MERGE_SAMPLE, KP_MISC, KP_ROLL_HIST, KP_ROLL_SCATTER, KP_PACK, KP_RP_SLOTS, KP_RP_SCATTER_NARROW, KP_SPECTRUM, KP_JOIN, KP_FA_MAPS, KP_FA_STATES, KP_FA_COUNT, KP_FA_COMPACT, KP_FA_SEGMENTS, KP_FA_PACK, KP_ROLL_SAMPLE, KP_ROLL_QUERY, KP_FA_REC_STARTS, KP_N
+  KP_RP_SCATTER, KP_MERGE_SUM, KP_REGION_SCAN, KP_MERGE_WRITE, KP_MERGE_SPILL, KP_PLACE, KP_MARKS, KP_LOOKUP, KP_WALK, KP_UG_WALK, KP_UG_FINISH, KP_MERGE_FUSED, KP_MERGE_SAMPLE, KP_MISC, KP_ROLL_HIST, KP_ROLL_SCATTER, KP_PACK, KP_RP_SLOTS, KP_RP_SCATTER_NARROW, KP_SPECTRUM, KP_JOIN, KP_FA_MAPS, KP_FA_STATES, KP_FA_COUNT, KP_FA_COMPACT, KP_FA_SEGMENTS, KP_FA_PACK, KP_ROLL_SAMPLE, KP_ROLL_QUERY, KP_FA_REC_STARTS, KP_READS_QUERY, KP_READS_MEDIAN, KP_N
 };
 static const char *kp_names[KP_N] = {
   "k_count_lines", "k_scan_chunks", "k_emit_reads", "k_count_keys", "k_hash_reads", "k_scan_*", "k_rp_prep",
   "k_rp_hist", "k_rp_scatter", "k_region_merge<summary>", "k_region_scan", "k_region_merge<write>",
-  "k_region_merge<spill>", "k_region_place", "k_denoise_marks", "k_lookup", "k_extend_forward+k_select_seeds", "k_ug_walk", "k_ug_check/emit/median/links", "k_region_merge<fused>", "k_region_merge<sample>", "misc", "k_roll_hist", "k_roll_scatter", "k_pack_reads", "k_rp_slot_cursors", "k_rp_scatter<narrow>", "k_region_spectrum", "k_region_join", "k_fa_maps", "k_fa_states", "k_fa_count", "k_fa_compact", "k_fa_segments+long+tail", "k_fa_pack", "k_roll_sample", "k_roll_query", "k_fa_rec_starts"};
+  "k_region_merge<spill>", "k_region_place", "k_denoise_marks", "k_lookup", "k_extend_forward+k_select_seeds", "k_ug_walk", "k_ug_check/emit/median/links", "k_region_merge<fused>", "k_region_merge<sample>", "misc", "k_roll_hist", "k_roll_scatter", "k_pack_reads", "k_rp_slot_cursors", "k_rp_scatter<narrow>", "k_region_spectrum", "k_region_join", "k_fa_maps", "k_fa_states", "k_fa_count", "k_fa_compact", "k_fa_segments+long+tail", "k_fa_pack", "k_roll_sample", "k_roll_query", "k_fa_rec_starts", "k_reads_query", "k_reads_median"};
 
 struct PendingEvent { int id; hipEvent_t a, b; };
 
@@ -217,6 +218,7 @@ struct shk_ctx : ShkStageBufs {
   struct ShkFront *front;       // shk_prepare_chunks: the front end (parse, hash, partition) of later batches on its own stream
   struct ShkFasta *fasta;       // shk_count_fasta, shk_query_fasta: their buffers and the states of their streams (allocated by the first call)
   uint32_t fasta_seg;           // k-mers per segment there (SHK_FASTA_SEGMENT)
+  struct ShkReads *reads;       // shk_query_reads: its buffers (allocated by the first call)
 };
 
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "libshk: %s failed: %s (%s:%d)\n", #x, hipGetErrorString(e_), __FILE__, __LINE__); return SHK_ERR_HIP; } } while (0)
@@ -503,11 +505,13 @@ extern "C" int shk_create(const shk_config *cfg, shk_ctx **out) {
 // (of a partly built context too: shk_create comes here from every failure)
 static void front_destroy(shk_ctx *c);
 static void fasta_destroy(shk_ctx *c);
+static void reads_destroy(shk_ctx *c);
 extern "C" void shk_destroy(shk_ctx *c) {
   if (!c) return;
   hipSetDevice(c->dev);
   front_destroy(c);
   fasta_destroy(c);
+  reads_destroy(c);
   if (c->stream) hipStreamSynchronize(c->stream);
   if (c->copy_stream) {
     hipStreamSynchronize(c->copy_stream);
@@ -2275,6 +2279,121 @@ extern "C" int shk_query_fasta(shk_ctx *c, const void *text, int text_on_device,
   if (q.kmers != P.nkmers) return SHK_ERR_CORRUPT;      // (every k-mer the segments hold has been answered, once)
   S->cur ^= 1; S->state = P.end_state; S->tail_len = P.new_tail;
   if (qstats) *qstats = q;
+  return SHK_OK;
+}
+
+// ------------------------------------------------------------------ FASTQ reads against the table (reads_kernels.hip)
+// What shk_query_reads keeps besides the context's buffers. Of those it borrows d_text (host text), the read arrays,
+// d_words[1] (the reads' 2-bit units, where pack_stage puts a counting batch's) and d_words[0] (the per-window values of
+// a call that wants a median or a host track). pack_stage owns d_nkeys and d_key_base (the units' flags and places), so
+// the windows of every read and their offsets have arrays of their own.
+struct ShkReads {
+  uint32_t *nwin = nullptr;         // [max_reads + 1] windows of every read
+  uint64_t *woff = nullptr;         // [max_reads + 2] ... scanned
+  shk_read_record *rec = nullptr;   // [max_reads] the records of a call whose rec is host memory
+  uint64_t *totals = nullptr;       // [4] kmers, present, solid, sum of the call
+};
+static void reads_destroy(shk_ctx *c) {
+  ShkReads *R = c->reads;
+  if (!R) return;
+  if (c->stream) hipStreamSynchronize(c->stream);
+  hipFree(R->nwin); hipFree(R->woff); hipFree(R->rec); hipFree(R->totals);
+  delete R;
+  c->reads = nullptr;
+}
+static int reads_init(shk_ctx *c) {
+  if (c->reads) return SHK_OK;
+  ShkReads *R = new ShkReads();
+  c->reads = R;
+  if (dmalloc(&R->nwin, c->max_reads + 1) || dmalloc(&R->woff, c->max_reads + 2) || dmalloc(&R->rec, c->max_reads + 1) || dmalloc(&R->totals, 4)) {
+    reads_destroy(c);      // (the next call tries again)
+    return SHK_ERR_HIP;
+  }
+  return SHK_OK;
+}
+
+extern "C" int shk_query_reads(shk_ctx *c, const void *text, int text_on_device, uint64_t text_bytes, const uint64_t *chunk_off,
+                               const uint64_t *chunk_len, uint32_t nchunks, uint32_t min_count, uint32_t flags, shk_read_record *rec,
+                               uint64_t rec_cap, int rec_on_device, uint64_t *nreads_out, shk_read_extent *ext, uint32_t *track,
+                               uint64_t track_cap, int track_on_device, uint64_t *nwindows, shk_reads_stats *rstats) {
+  static_assert(sizeof(shk_read_record) == 32 && sizeof(shk_read_extent) == 16, "the kernel stores a record as two 16-byte halves");
+  if (!c || !text || !rec || !nreads_out || (flags & ~SHK_READS_MEDIAN)) return SHK_ERR_ARG;
+  if (c->cfg.num_shards > 1 || !text_aligned(text, text_on_device)) return SHK_ERR_ARG;
+  if (c->front && c->front->count) return SHK_ERR_BATCH;     // (the call borrows the batch buffers their words may lie in)
+  if (!chunk_labels_ok(nchunks, 0, 1)) return SHK_ERR_BATCH;
+  if (!chunk_off || !chunk_len) return SHK_ERR_ARG;
+  HIPCHK(hipSetDevice(c->dev));
+  { int rc = table_sync(c); if (rc) return rc; }
+  if (upload_wait(c, text, text_on_device, c->stream)) return SHK_ERR_HIP;
+  { int rc = reads_init(c); if (rc) return rc; }
+  ShkReads *R = c->reads;
+  const uint8_t *dtext;
+  uint64_t nreads;
+  int rc = parse_stage(c, c, text, text_on_device, text_bytes, chunk_off, chunk_len, nchunks, &dtext, &nreads);
+  if (rc) return finish(c, rc);
+  const uint32_t t = c->threads < 256 ? c->threads : 256;
+  const bool small = c->threads < 512;      // (small workgroups: the CPU emulator build of the tests)
+  { ProfScope ps(c, KP_MISC);
+    const uint64_t blocks = nreads / t + 1;
+    hipLaunchKernelGGL(k_reads_windows, dim3((uint32_t)(blocks < 4096 ? blocks : 4096)), dim3(t), 0, c->stream, (const uint64_t *)c->d_rd_start,
+                       (const uint64_t *)c->d_rd_end, nreads, c->cfg.k, R->nwin, c->d_err); }
+  if (run_scan<uint32_t>(c, c, R->nwin, nreads, nullptr, R->woff)) return finish(c, SHK_ERR_HIP);
+  uint64_t nwin = 0;
+  HIPCHK(hipMemcpyAsync(&nwin, R->woff + nreads, 8, hipMemcpyDeviceToHost, c->stream));
+  rc = finish(c, SHK_OK);      // (malformed text, a read of more than 65535 bases: nothing has been written yet)
+  if (rc) return rc;
+  *nreads_out = nreads;
+  if (nwindows) *nwindows = nwin;
+  if (rec_cap < nreads || nwin > c->cfg.max_batch_keys || (track && track_cap < nwin)) return SHK_ERR_BATCH;
+  shk_reads_stats q = {nreads, 0, 0, 0, 0};
+  if (nreads == 0) { if (rstats) *rstats = q; return SHK_OK; }
+  const bool median = (flags & SHK_READS_MEDIAN) != 0;
+  // the per-window values: straight into a device track; else, for a host track or the median, into d_words[0]
+  // (max_batch_keys words of 8 bytes for at most max_batch_keys entries of 4)
+  uint32_t *dwin = nullptr;
+  if (nwin && (track || median)) dwin = track && track_on_device ? track : (uint32_t *)c->d_words[0];
+  shk_read_record *drec = rec_on_device ? rec : R->rec;
+  ShkRollArgs P;
+  roll_args(c, c, P, dtext, text_bytes, 0, 1);
+  rc = pack_stage(c, c, P, nreads, text_bytes, c->d_words[1]);
+  if (rc) return finish(c, rc);
+  HIPCHK(hipMemsetAsync(R->totals, 0, 32, c->stream));
+  {
+    ShkReadsArgs A;
+    A.text = dtext; A.rd_start = c->d_rd_start; A.rd_end = c->d_rd_end; A.nreads = nreads;
+    A.pk = P.pk; A.pk_base = P.pk_base; A.pk_flag = P.pk_flag; A.woff = R->woff;
+    A.k = c->cfg.k; A.hb = c->cfg.hb; A.tab = c->tab[c->cur]; A.q_lo = c->q_lo; A.nslots = c->nslots; A.min_count = min_count;
+    A.median = median ? 0 : SHK_QUERY_NONE; A.win = dwin; A.rec = drec; A.totals = R->totals;
+    ProfScope ps(c, KP_READS_QUERY);
+    const uint64_t blocks = nreads / t + 1, most = small ? 4 : 4096;
+    hipLaunchKernelGGL(k_reads_query, dim3((uint32_t)(blocks < most ? blocks : most)), dim3(t), 0, c->stream, A);
+  }
+  if (median && nwin) {
+    ProfScope ps(c, KP_READS_MEDIAN);
+    const uint64_t blocks = nreads / (t / SHK_READS_GROUP) + 1, most = small ? 4 : 16384;
+    hipLaunchKernelGGL(k_reads_median, dim3((uint32_t)(blocks < most ? blocks : most)), dim3(t), 0, c->stream, (const uint32_t *)dwin,
+                       (const uint64_t *)R->woff, nreads, drec);
+  }
+  HIPCHK(hipGetLastError());
+  // (every capacity has been compared above: from here on only the runtime itself can fail)
+  std::vector<uint64_t> hst, hen;
+  std::vector<uint16_t> hch;
+  uint64_t tot[4] = {0, 0, 0, 0};
+  if (!rec_on_device) HIPCHK(hipMemcpyAsync(rec, R->rec, nreads * 32, hipMemcpyDeviceToHost, c->stream));
+  if (track && !track_on_device && nwin) HIPCHK(hipMemcpyAsync(track, dwin, nwin * 4, hipMemcpyDeviceToHost, c->stream));
+  if (ext) {
+    hst.resize(nreads); hen.resize(nreads); hch.resize(nreads);
+    HIPCHK(hipMemcpyAsync(hst.data(), c->d_rd_start, nreads * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(hen.data(), c->d_rd_end, nreads * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(hch.data(), c->d_rd_chunk, nreads * 2, hipMemcpyDeviceToHost, c->stream));
+  }
+  HIPCHK(hipMemcpyAsync(tot, R->totals, 32, hipMemcpyDeviceToHost, c->stream));
+  rc = finish(c, SHK_OK);
+  if (rc) return rc;
+  if (ext)
+    for (uint64_t r = 0; r < nreads; r++) { ext[r].seq_off = hst[r]; ext[r].seq_len = (uint32_t)(hen[r] - hst[r]); ext[r].chunk = hch[r]; }
+  q.kmers = tot[0]; q.present = tot[1]; q.solid = tot[2]; q.sum = tot[3];
+  if (rstats) *rstats = q;
   return SHK_OK;
 }
 

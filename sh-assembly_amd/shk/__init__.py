@@ -63,6 +63,35 @@ class QueryStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+READS_MEDIAN = 1              # SHK_READS_MEDIAN (include/shk.h)
+
+
+class ReadRecord(C.Structure):
+    """shk_read_record (include/shk.h)"""
+    _fields_ = [("sum", C.c_uint64), ("kmers", C.c_uint32), ("present", C.c_uint32), ("solid", C.c_uint32), ("min", C.c_uint32),
+                ("median", C.c_uint32), ("max", C.c_uint32)]
+
+
+class ReadExtent(C.Structure):
+    """shk_read_extent (include/shk.h)"""
+    _fields_ = [("seq_off", C.c_uint64), ("seq_len", C.c_uint32), ("chunk", C.c_uint32)]
+
+
+class ReadsStats(C.Structure):
+    """shk_reads_stats (include/shk.h)"""
+    _fields_ = [("reads", C.c_uint64), ("kmers", C.c_uint64), ("present", C.c_uint64), ("solid", C.c_uint64), ("sum", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+def _struct_dtype(cls):
+    """the numpy structured dtype of a ctypes structure of plain integers"""
+    import numpy as np
+    return np.dtype({"names": [f for f, _ in cls._fields_], "formats": [np.dtype(t) for _, t in cls._fields_],
+                     "offsets": [getattr(cls, f).offset for f, _ in cls._fields_], "itemsize": C.sizeof(cls)})
+
+
 class SampleStats(C.Structure):
     """shk_sample_stats (include/shk.h)"""
     _fields_ = [("kmers", C.c_uint64), ("kept", C.c_uint64)]
@@ -103,7 +132,7 @@ EXPORTS = ["shk_create", "shk_destroy", "shk_count_chunks", "shk_hash_chunks", "
            "shk_lookup", "shk_profile_enable", "shk_profile_get", "shk_profile_reset", "shk_strerror",
            "shk_last_error_bits", "shk_insert_counted", "shk_dump", "shk_merge", "shk_multi_merge", "shk_import_shards", "shk_table_ptr", "shk_unitigs_add_reads",
            "shk_spectrum", "shk_inner_product", "shk_magnitude", "shk_intersect", "shk_count_fasta", "shk_split_batches", "shk_sample_chunks", "shk_query_fasta",
-           "shk_prefetch_passes"]
+           "shk_prefetch_passes", "shk_query_reads"]
 
 _libs = {}
 
@@ -124,6 +153,7 @@ def load(path=None):
     L.shk_count_chunks.argtypes = [vp, vp, i32, u64, pu64, pu64, u32, C.POINTER(BatchStats)]
     L.shk_count_fasta.argtypes = [vp, vp, i32, u64, i32, C.POINTER(BatchStats), C.POINTER(FastaStats)]
     L.shk_query_fasta.argtypes = [vp, vp, i32, u64, i32, u32, vp, u64, i32, vp, u32, C.POINTER(u32), C.POINTER(QueryStats)]
+    L.shk_query_reads.argtypes = [vp, vp, i32, u64, pu64, pu64, u32, u32, u32, vp, u64, i32, pu64, vp, vp, u64, i32, pu64, C.POINTER(ReadsStats)]
     L.shk_sample_chunks.argtypes = [vp, vp, i32, u64, pu64, pu64, u32, u32, C.POINTER(BatchStats), C.POINTER(SampleStats)]
     L.shk_hash_chunks.argtypes = [vp, vp, i32, u64, pu64, pu64, u32, C.POINTER(vp), pu64]
     L.shk_upload_text.argtypes = [vp, vp, u64, C.POINTER(vp)]
@@ -317,6 +347,39 @@ class Context:
             self._chk(rc)
             break
         return qs.as_dict(), rec[:nrec.value].copy(), (track[:qs.bases].copy() if want_track else None)
+
+    def query_reads(self, text, chunk_off, chunk_len, min_count=2, median=False, want_track=False, want_extents=False,
+                    on_device=False, text_bytes=None):
+        """FASTQ chunks against the table (shk_query_reads); text as in count_chunks. Returns (statistics dict, the reads'
+        records as a structured array with ReadRecord's fields, their extents as one with ReadExtent's or None, the track
+        as a uint32 array with one entry per window or None). The call is repeated once with larger buffers when it
+        answers that there are more reads or windows than the first guess."""
+        import numpy as np
+        if on_device or isinstance(text, int):
+            ptr, n = C.c_void_p(int(text)), int(text_bytes)
+        else:
+            buf = (C.c_char * max(len(text), 1)).from_buffer_copy(bytes(text) or b"\0") if not isinstance(text, C.Array) else text
+            ptr, n = C.cast(buf, C.c_void_p), len(text)
+        span = sum(int(x) for x in chunk_len)
+        rec_cap, track_cap = span // 64 + 64, (span // 2 + 64 if want_track else 0)
+        nreads, nwin, rs = C.c_uint64(), C.c_uint64(), ReadsStats()
+        for _ in range(2):
+            rec = np.zeros(max(rec_cap, 1), dtype=_struct_dtype(ReadRecord))
+            ext = np.zeros(max(rec_cap, 1), dtype=_struct_dtype(ReadExtent)) if want_extents else None
+            track = np.empty(max(track_cap, 1), dtype=np.uint32) if want_track else None
+            rc = self.L.shk_query_reads(self.h, ptr, 1 if on_device else 0, n, self._tab(chunk_off), self._tab(chunk_len), len(chunk_off),
+                                        int(min_count), READS_MEDIAN if median else 0, C.c_void_p(rec.ctypes.data), rec_cap, 0, C.byref(nreads),
+                                        C.c_void_p(ext.ctypes.data) if want_extents else None,
+                                        C.c_void_p(track.ctypes.data) if want_track else None, track_cap, 0, C.byref(nwin), C.byref(rs))
+            if rc == -7 and (nreads.value > rec_cap or (want_track and nwin.value > track_cap)):
+                rec_cap, track_cap = max(rec_cap, nreads.value), (max(track_cap, nwin.value) if want_track else 0)
+                nreads.value, nwin.value = 0, 0
+                continue
+            break
+        self._chk(rc)
+        nr = nreads.value
+        return (rs.as_dict(), rec[:nr].copy(), ext[:nr].copy() if want_extents else None,
+                track[:nwin.value].copy() if want_track else None)
 
     def sample_chunks(self, text, chunk_off, chunk_len, sample_bits, on_device=False, text_bytes=None):
         """count the k-mers whose canonical hash has bits [hb, hb + sample_bits) zero (shk_sample_chunks); text as in
