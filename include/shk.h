@@ -37,6 +37,8 @@
  *                         the table: per-base counts and per-record totals
  *   shk_query_reads       (no counterpart: the reference answers one hashed key at a time, qf_count_key_value) FASTQ reads
  *                         against the table: per-read k-mer statistics, median count, per-window counts
+ *   shk_correct_reads     (no counterpart: CQF-deNoise repairs the table, nothing repairs the reads) substitution errors of
+ *                         FASTQ reads against the table: per read the edits that make its weak windows solid
  *   shk_sample_chunks     (no counterpart: the reference's README sends the user to ntCard) -N -n -e from the reads themselves
  *   shk_import_shards     (no counterpart: the reference is one process) quotient-range shards -> the single table
  *   shk_stats             runtime->nelts / ndistinct_elts / num_deNoise    cqf/CQF_mt.h:277-288
@@ -298,6 +300,65 @@ int shk_query_reads(shk_ctx *ctx, const void *text, int text_on_device, uint64_t
                     shk_read_extent *ext,                                   /* may be NULL; host memory, rec_cap entries */
                     uint32_t *track, uint64_t track_cap, int track_on_device, uint64_t *nwindows,   /* track may be NULL */
                     shk_reads_stats *rstats /* may be NULL */);
+
+/* ---- substitution errors of FASTQ reads repaired against the table (no counterpart in the reference: CQF-deNoise takes
+ * the false k-mers out of the table, nothing takes them out of the reads). A read whose k-mers are solid, then weak for k
+ * windows, then solid again holds one wrong base, and the table says which base belongs there. The call returns edits,
+ * not text: shk/correct.py's apply_edits puts them into a copy of the text.
+ *   - Text, chunks, the order of the reads, *nreads and ext: exactly shk_query_reads' contract.
+ *   - Candidates: a read is a candidate when its sequence line has k <= seq_len <= 65535 bytes and every byte is one of
+ *     A C G T a c g t. A shorter read is flagged SHK_CORRECT_SHORT (whatever it holds), a read of at least k bytes with
+ *     any other byte SHK_CORRECT_NONBASE (a '\r' in front of the line feed belongs to the sequence line, so every read of
+ *     a CRLF file is one); both are left alone, with edits = unfixable = ambiguous = 0.
+ *   - The rule. A window is solid when its k-mer's count is >= min_count; its key is the one the counting paths give it
+ *     (canonical ntHash masked to hb bits). W = seq_len - k + 1. S is the read, mutable; budget starts at max_edits.
+ *         forward(S): prev = false
+ *                     for j in 0 .. W-1:
+ *                         solid = count(S[j:j+k]) >= min_count                 (S as it is NOW, earlier edits included)
+ *                         if not solid and prev:
+ *                             if budget == 0: flags |= SHK_CORRECT_CAPPED
+ *                             else: p = j + k - 1                              (the suspect: the base window j adds)
+ *                                   valid = the bases b != S[p] for which every window j .. min(j + check, W - 1) of S
+ *                                           with S[p] = b is solid
+ *                                   one:     S[p] = b, the edit (p, b) is recorded, budget -= 1, solid = true
+ *                                   none:    unfixable += 1
+ *                                   several: ambiguous += 1                    (no tie-break, no "highest count")
+ *                         prev = solid
+ *         correct(S): forward(S); forward(the reverse complement of S), its edits recorded in S's coordinates and strand
+ *     A larger check is more conservative. 0 <= check <= 255, 1 <= max_edits <= 16, min_count >= 1.
+ *   - rec[r] (host memory unless rec_on_device != 0): what the rule did to read r, and the flags above.
+ *   - edits (a host pointer unless edits_on_device != 0; rec_cap * max_edits entries): entry edits[r * max_edits + e], for
+ *     e < rec[r].edits, is pos | code << 16: pos = the offset in the sequence line, code = the new base, A C G T = 0 1 2 3.
+ *     The entries stand in the order the edits were made: those of the forward pass ascending, then those of the backward
+ *     pass descending. A position may appear twice; the later entry wins. Entries behind rec[r].edits are unspecified.
+ *   - The caller's text is never written: device text is byte for byte what it was.
+ *   - cstats (may be NULL): reads = *nreads, and over the candidates: their number, those with an edit, and the sums of
+ *     edits, unfixable and ambiguous; capped = the reads flagged SHK_CORRECT_CAPPED.
+ *   - It is a reader: it launches the pending lazy placement first, reads with mark mode 2, and changes no byte of the
+ *     table and no runtime counter. The 2-bit staging of the batch is consumed (the edits are made there).
+ * Errors: nothing is written to rec, ext or edits. SHK_ERR_ARG for a sharded context, device text that is not 16-byte
+ * aligned, NULL rec, edits, nreads or chunk arrays, min_count == 0, check > 255, max_edits outside 1 .. 16; SHK_ERR_BATCH
+ * for shk_query_reads' reasons (nchunks outside 1 .. 4096, text or reads beyond the context's capacities, batches prepared
+ * and not yet counted), for a batch whose 2-bit units the staging buffer cannot hold (text_bytes / 64 + reads + 1 units
+ * of 16 bytes against max_batch_keys / 2 - 1: the bound the counting path computes -- SHK_NO_PACK, that path's
+ * measurement switch, does not apply here), and for rec_cap < *nreads, with *nreads still set so that the call can be
+ * repeated; SHK_ERR_FASTQ for a read of more than 65535 bases.
+ * A context that has answered such a call keeps the records and the edit lists of its largest batch on the device (16 +
+ * 4 * max_edits bytes per read), only as far as the caller's are host memory. */
+#define SHK_CORRECT_SHORT    1u   /* fewer than k bytes: nothing to do */
+#define SHK_CORRECT_NONBASE  2u   /* holds a byte that is no base: left alone */
+#define SHK_CORRECT_CAPPED   4u   /* a suspect was met with the budget used up */
+typedef struct shk_correct_record { uint32_t edits, unfixable, ambiguous, flags; } shk_correct_record;   /* 16 bytes */
+typedef struct shk_correct_stats { uint64_t reads, candidates, edited_reads, edits, unfixable, ambiguous, capped; } shk_correct_stats;
+int shk_correct_reads(shk_ctx *ctx, const void *text, int text_on_device, uint64_t text_bytes,
+                      const uint64_t *chunk_off, const uint64_t *chunk_len, uint32_t nchunks,
+                      uint32_t min_count, uint32_t check, uint32_t max_edits,
+                      shk_correct_record *rec, uint64_t rec_cap, int rec_on_device, uint64_t *nreads,
+                      shk_read_extent *ext,                 /* may be NULL; host memory, rec_cap entries */
+                      uint32_t *edits, int edits_on_device, /* rec_cap * max_edits entries */
+                      shk_correct_stats *cstats             /* may be NULL */);
+/* table lookups of the context's last shk_correct_reads (measurement: tools/bench_correct.py divides them by the windows) */
+uint64_t shk_correct_lookups(shk_ctx *ctx);
 
 /* ---- a hash-sampled spectrum of the reads (no counterpart in the reference, whose README sends the user to ntCard for
  * the -N -n -e its command line wants). Hashes every k-mer of the FASTQ chunks exactly as shk_count_chunks does (the

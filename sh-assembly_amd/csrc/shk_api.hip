@@ -26,17 +26,18 @@
 #include "fasta_kernels.hip"
 #include "query_kernels.hip"
 #include "reads_kernels.hip"
+#include "correct_kernels.hip"
 
 #define SHK_SLACK 256  // bytes of slack behind buffers read with wide loads
 
 enum {
   KP_COUNT_LINES, KP_SCAN_CHUNKS, KP_EMIT_READS, KP_COUNT_KEYS, KP_HASH, KP_SCAN, KP_RP_PREP, KP_RP_HIST,
-  KP_RP_SCATTER, KP_MERGE_SUM, KP_REGION_SCAN, KP_MERGE_WRITE, KP_MERGE_SPILL, KP_PLACE, KP_MARKS, KP_LOOKUP, KP_WALK, KP_UG_WALK, KP_UG_FINISH, KP_MERGE_FUSED, KP_MERGE_SAMPLE, KP_MISC, KP_ROLL_HIST, KP_ROLL_SCATTER, KP_PACK, KP_RP_SLOTS, KP_RP_SCATTER_NARROW, KP_SPECTRUM, KP_JOIN, KP_FA_MAPS, KP_FA_STATES, KP_FA_COUNT, KP_FA_COMPACT, KP_FA_SEGMENTS, KP_FA_PACK, KP_ROLL_SAMPLE, KP_ROLL_QUERY, KP_FA_REC_STARTS, KP_READS_QUERY, KP_READS_MEDIAN, KP_N
+  KP_RP_SCATTER, KP_MERGE_SUM, KP_REGION_SCAN, KP_MERGE_WRITE, KP_MERGE_SPILL, KP_PLACE, KP_MARKS, KP_LOOKUP, KP_WALK, KP_UG_WALK, KP_UG_FINISH, KP_MERGE_FUSED, KP_MERGE_SAMPLE, KP_MISC, KP_ROLL_HIST, KP_ROLL_SCATTER, KP_PACK, KP_RP_SLOTS, KP_RP_SCATTER_NARROW, KP_SPECTRUM, KP_JOIN, KP_FA_MAPS, KP_FA_STATES, KP_FA_COUNT, KP_FA_COMPACT, KP_FA_SEGMENTS, KP_FA_PACK, KP_ROLL_SAMPLE, KP_ROLL_QUERY, KP_FA_REC_STARTS, KP_READS_QUERY, KP_READS_MEDIAN, KP_READS_CORRECT, KP_N
 };
 static const char *kp_names[KP_N] = {
   "k_count_lines", "k_scan_chunks", "k_emit_reads", "k_count_keys", "k_hash_reads", "k_scan_*", "k_rp_prep",
   "k_rp_hist", "k_rp_scatter", "k_region_merge<summary>", "k_region_scan", "k_region_merge<write>",
-  "k_region_merge<spill>", "k_region_place", "k_denoise_marks", "k_lookup", "k_extend_forward+k_select_seeds", "k_ug_walk", "k_ug_check/emit/median/links", "k_region_merge<fused>", "k_region_merge<sample>", "misc", "k_roll_hist", "k_roll_scatter", "k_pack_reads", "k_rp_slot_cursors", "k_rp_scatter<narrow>", "k_region_spectrum", "k_region_join", "k_fa_maps", "k_fa_states", "k_fa_count", "k_fa_compact", "k_fa_segments+long+tail", "k_fa_pack", "k_roll_sample", "k_roll_query", "k_fa_rec_starts", "k_reads_query", "k_reads_median"};
+  "k_region_merge<spill>", "k_region_place", "k_denoise_marks", "k_lookup", "k_extend_forward+k_select_seeds", "k_ug_walk", "k_ug_check/emit/median/links", "k_region_merge<fused>", "k_region_merge<sample>", "misc", "k_roll_hist", "k_roll_scatter", "k_pack_reads", "k_rp_slot_cursors", "k_rp_scatter<narrow>", "k_region_spectrum", "k_region_join", "k_fa_maps", "k_fa_states", "k_fa_count", "k_fa_compact", "k_fa_segments+long+tail", "k_fa_pack", "k_roll_sample", "k_roll_query", "k_fa_rec_starts", "k_reads_query", "k_reads_median", "k_reads_correct"};
 
 struct PendingEvent { int id; hipEvent_t a, b; };
 
@@ -219,6 +220,7 @@ struct shk_ctx : ShkStageBufs {
   struct ShkFasta *fasta;       // shk_count_fasta, shk_query_fasta: their buffers and the states of their streams (allocated by the first call)
   uint32_t fasta_seg;           // k-mers per segment there (SHK_FASTA_SEGMENT)
   struct ShkReads *reads;       // shk_query_reads: its buffers (allocated by the first call)
+  struct ShkCorrect *correct;   // shk_correct_reads: its buffers (allocated by the first call)
 };
 
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "libshk: %s failed: %s (%s:%d)\n", #x, hipGetErrorString(e_), __FILE__, __LINE__); return SHK_ERR_HIP; } } while (0)
@@ -506,12 +508,14 @@ extern "C" int shk_create(const shk_config *cfg, shk_ctx **out) {
 static void front_destroy(shk_ctx *c);
 static void fasta_destroy(shk_ctx *c);
 static void reads_destroy(shk_ctx *c);
+static void correct_destroy(shk_ctx *c);
 extern "C" void shk_destroy(shk_ctx *c) {
   if (!c) return;
   hipSetDevice(c->dev);
   front_destroy(c);
   fasta_destroy(c);
   reads_destroy(c);
+  correct_destroy(c);
   if (c->stream) hipStreamSynchronize(c->stream);
   if (c->copy_stream) {
     hipStreamSynchronize(c->copy_stream);
@@ -663,13 +667,15 @@ static int hash_stage(const shk_ctx *c, ShkStageBufs *b, const void *text, int o
 
 // 2-bit staging of the batch's reads for the roll kernels (k_pack_reads), in `buf` = a buffer of max_batch_keys words that
 // nothing else uses until the roll kernels are done. Leaves A.pk null (text path for every read) when the buffer cannot
-// hold the batch's units or SHK_NO_PACK is set (measurement).
-static int pack_stage(const shk_ctx *c, ShkStageBufs *b, ShkRollArgs &A, uint64_t nreads, uint64_t text_bytes, uint64_t *buf) {
+// hold the batch's units or SHK_NO_PACK is set (measurement; a caller that has no text path passes no_pack_switch = false).
+static uint64_t pack_cap_units(const shk_ctx *c) { return c->cfg.max_batch_keys / 2 > 1 ? c->cfg.max_batch_keys / 2 - 1 : 0; }
+static int pack_stage(const shk_ctx *c, ShkStageBufs *b, ShkRollArgs &A, uint64_t nreads, uint64_t text_bytes, uint64_t *buf,
+                      bool no_pack_switch = true) {
   A.pk = nullptr; A.pk_base = nullptr; A.pk_flag = nullptr;
   // units <= sum over reads of (len / 64 + 1) <= text_bytes / 64 + nreads when no two chunks overlap (k_pack_reads leaves
   // the reads that do not fit on the text path); 16 bytes of slack for the roll kernels' 16-byte fetches
-  const uint64_t cap_units = c->cfg.max_batch_keys / 2 > 1 ? c->cfg.max_batch_keys / 2 - 1 : 0;
-  if (getenv("SHK_NO_PACK") || text_bytes / 64 + nreads + 1 > cap_units) return SHK_OK;
+  const uint64_t cap_units = pack_cap_units(c);
+  if ((no_pack_switch && getenv("SHK_NO_PACK")) || text_bytes / 64 + nreads + 1 > cap_units) return SHK_OK;
   ProfScope ps(c, b, KP_PACK);
   const uint32_t t = c->threads < 256 ? c->threads : 256;
   { const uint64_t blocks = nreads / t + 1;
@@ -2394,6 +2400,119 @@ extern "C" int shk_query_reads(shk_ctx *c, const void *text, int text_on_device,
     for (uint64_t r = 0; r < nreads; r++) { ext[r].seq_off = hst[r]; ext[r].seq_len = (uint32_t)(hen[r] - hst[r]); ext[r].chunk = hch[r]; }
   q.kmers = tot[0]; q.present = tot[1]; q.solid = tot[2]; q.sum = tot[3];
   if (rstats) *rstats = q;
+  return SHK_OK;
+}
+
+// ------------------------------------------------------------------ FASTQ reads repaired against the table (correct_kernels.hip)
+// What shk_correct_reads keeps besides the context's buffers. It borrows what shk_query_reads borrows (d_text for host
+// text, the read arrays, d_words[1] for the reads' 2-bit units, into which the kernel writes its edits); the records and
+// the edit lists of a call whose arrays are host memory have buffers here that grow with the largest batch.
+struct ShkCorrect {
+  shk_correct_record *rec = nullptr; uint64_t rec_cap = 0;
+  uint32_t *edits = nullptr; uint64_t edits_cap = 0;
+  uint64_t *totals = nullptr;       // [SHK_CORRECT_TOTALS]
+  uint64_t lookups = 0;             // of the last call (shk_correct_lookups)
+};
+static void correct_destroy(shk_ctx *c) {
+  ShkCorrect *R = c->correct;
+  if (!R) return;
+  if (c->stream) hipStreamSynchronize(c->stream);
+  hipFree(R->rec); hipFree(R->edits); hipFree(R->totals);
+  delete R;
+  c->correct = nullptr;
+}
+template <typename T>
+static int correct_grow(shk_ctx *c, T **buf, uint64_t *cap, uint64_t want) {
+  if (want <= *cap) return SHK_OK;
+  HIPCHK(hipStreamSynchronize(c->stream));
+  hipFree(*buf); *buf = nullptr; *cap = 0;
+  if (dmalloc(buf, want + want / 2)) return SHK_ERR_HIP;
+  *cap = want + want / 2;
+  return SHK_OK;
+}
+
+extern "C" uint64_t shk_correct_lookups(shk_ctx *c) { return c && c->correct ? c->correct->lookups : 0; }
+
+extern "C" int shk_correct_reads(shk_ctx *c, const void *text, int text_on_device, uint64_t text_bytes, const uint64_t *chunk_off,
+                                 const uint64_t *chunk_len, uint32_t nchunks, uint32_t min_count, uint32_t check, uint32_t max_edits,
+                                 shk_correct_record *rec, uint64_t rec_cap, int rec_on_device, uint64_t *nreads_out, shk_read_extent *ext,
+                                 uint32_t *edits, int edits_on_device, shk_correct_stats *cstats) {
+  static_assert(sizeof(shk_correct_record) == 16, "the kernel stores a record as one 16-byte store");
+  if (!c || !text || !rec || !edits || !nreads_out || min_count == 0 || check > 255 || max_edits < 1 || max_edits > 16) return SHK_ERR_ARG;
+  if (c->cfg.num_shards > 1 || !text_aligned(text, text_on_device)) return SHK_ERR_ARG;
+  if (c->front && c->front->count) return SHK_ERR_BATCH;     // (the call borrows the batch buffers their words may lie in)
+  if (!chunk_labels_ok(nchunks, 0, 1)) return SHK_ERR_BATCH;
+  if (!chunk_off || !chunk_len) return SHK_ERR_ARG;
+  HIPCHK(hipSetDevice(c->dev));
+  { int rc = table_sync(c); if (rc) return rc; }
+  if (upload_wait(c, text, text_on_device, c->stream)) return SHK_ERR_HIP;
+  if (!c->correct) {
+    c->correct = new ShkCorrect();
+    if (dmalloc(&c->correct->totals, SHK_CORRECT_TOTALS)) { correct_destroy(c); return SHK_ERR_HIP; }      // (the next call tries again)
+  }
+  ShkCorrect *R = c->correct;
+  const uint8_t *dtext;
+  uint64_t nreads;
+  int rc = parse_stage(c, c, text, text_on_device, text_bytes, chunk_off, chunk_len, nchunks, &dtext, &nreads);
+  if (rc) return finish(c, rc);
+  const uint32_t t = c->threads < 256 ? c->threads : 256;
+  const bool small = c->threads < 512;      // (small workgroups: the CPU emulator build of the tests)
+  { ProfScope ps(c, KP_MISC);
+    const uint64_t blocks = nreads / t + 1;
+    hipLaunchKernelGGL(k_correct_check, dim3((uint32_t)(blocks < 4096 ? blocks : 4096)), dim3(t), 0, c->stream, (const uint64_t *)c->d_rd_start,
+                       (const uint64_t *)c->d_rd_end, nreads, c->d_err); }
+  // the units go into library memory only, so they are packed before the text has been judged: one wait for both answers
+  ShkRollArgs P;
+  roll_args(c, c, P, dtext, text_bytes, 0, 1);
+  P.pk = nullptr;
+  if (nreads) { rc = pack_stage(c, c, P, nreads, text_bytes, c->d_words[1], false); if (rc) return finish(c, rc); }
+  uint64_t units = 0;
+  if (P.pk) HIPCHK(hipMemcpyAsync(&units, c->d_key_base + nreads, 8, hipMemcpyDeviceToHost, c->stream));
+  rc = finish(c, SHK_OK);      // (malformed text, a read of more than 65535 bases: nothing has been written yet)
+  if (rc) return rc;
+  *nreads_out = nreads;
+  if (rec_cap < nreads || (nreads && (!P.pk || units > pack_cap_units(c)))) return SHK_ERR_BATCH;
+  shk_correct_stats q = {nreads, 0, 0, 0, 0, 0, 0};
+  R->lookups = 0;
+  if (nreads == 0) { if (cstats) *cstats = q; return SHK_OK; }
+  if (!rec_on_device) { rc = correct_grow(c, &R->rec, &R->rec_cap, nreads); if (rc) return rc; }
+  if (!edits_on_device) { rc = correct_grow(c, &R->edits, &R->edits_cap, nreads * max_edits); if (rc) return rc; }
+  shk_correct_record *drec = rec_on_device ? rec : R->rec;
+  uint32_t *dedits = edits_on_device ? edits : R->edits;
+  HIPCHK(hipMemsetAsync(R->totals, 0, SHK_CORRECT_TOTALS * 8, c->stream));
+  {
+    ShkCorrectArgs A;
+    A.rd_start = c->d_rd_start; A.rd_end = c->d_rd_end; A.nreads = nreads;
+    A.pk = (ShkQuad *)c->d_words[1]; A.pk_base = P.pk_base; A.pk_flag = P.pk_flag;
+    A.k = c->cfg.k; A.hb = c->cfg.hb; A.tab = c->tab[c->cur]; A.q_lo = c->q_lo; A.nslots = c->nslots;
+    A.min_count = min_count; A.check = check; A.max_edits = max_edits;
+    A.rec = drec; A.edits = dedits; A.totals = R->totals;
+    ProfScope ps(c, KP_READS_CORRECT);
+    const uint64_t blocks = nreads / t + 1, most = small ? 4 : 4096;
+    hipLaunchKernelGGL(k_reads_correct, dim3((uint32_t)(blocks < most ? blocks : most)), dim3(t), 0, c->stream, A);
+  }
+  HIPCHK(hipGetLastError());
+  // (every capacity has been compared above: from here on only the runtime itself can fail)
+  std::vector<uint64_t> hst, hen;
+  std::vector<uint16_t> hch;
+  uint64_t tot[SHK_CORRECT_TOTALS] = {0, 0, 0, 0, 0, 0, 0};
+  if (!rec_on_device) HIPCHK(hipMemcpyAsync(rec, R->rec, nreads * 16, hipMemcpyDeviceToHost, c->stream));
+  if (!edits_on_device) HIPCHK(hipMemcpyAsync(edits, R->edits, nreads * max_edits * 4, hipMemcpyDeviceToHost, c->stream));
+  if (ext) {
+    hst.resize(nreads); hen.resize(nreads); hch.resize(nreads);
+    HIPCHK(hipMemcpyAsync(hst.data(), c->d_rd_start, nreads * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(hen.data(), c->d_rd_end, nreads * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(hch.data(), c->d_rd_chunk, nreads * 2, hipMemcpyDeviceToHost, c->stream));
+  }
+  HIPCHK(hipMemcpyAsync(tot, R->totals, SHK_CORRECT_TOTALS * 8, hipMemcpyDeviceToHost, c->stream));
+  rc = finish(c, SHK_OK);
+  if (rc) return rc;
+  if (ext)
+    for (uint64_t r = 0; r < nreads; r++) { ext[r].seq_off = hst[r]; ext[r].seq_len = (uint32_t)(hen[r] - hst[r]); ext[r].chunk = hch[r]; }
+  q.candidates = tot[CT_CANDIDATES]; q.edited_reads = tot[CT_EDITED]; q.edits = tot[CT_EDITS]; q.unfixable = tot[CT_UNFIXABLE];
+  q.ambiguous = tot[CT_AMBIGUOUS]; q.capped = tot[CT_CAPPED];
+  R->lookups = tot[CT_LOOKUPS];
+  if (cstats) *cstats = q;
   return SHK_OK;
 }
 

@@ -85,6 +85,23 @@ class ReadsStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+CORRECT_SHORT, CORRECT_NONBASE, CORRECT_CAPPED = 1, 2, 4      # SHK_CORRECT_* (include/shk.h)
+
+
+class CorrectRecord(C.Structure):
+    """shk_correct_record (include/shk.h)"""
+    _fields_ = [("edits", C.c_uint32), ("unfixable", C.c_uint32), ("ambiguous", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class CorrectStats(C.Structure):
+    """shk_correct_stats (include/shk.h)"""
+    _fields_ = [("reads", C.c_uint64), ("candidates", C.c_uint64), ("edited_reads", C.c_uint64), ("edits", C.c_uint64),
+                ("unfixable", C.c_uint64), ("ambiguous", C.c_uint64), ("capped", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 def _struct_dtype(cls):
     """the numpy structured dtype of a ctypes structure of plain integers"""
     import numpy as np
@@ -132,7 +149,7 @@ EXPORTS = ["shk_create", "shk_destroy", "shk_count_chunks", "shk_hash_chunks", "
            "shk_lookup", "shk_profile_enable", "shk_profile_get", "shk_profile_reset", "shk_strerror",
            "shk_last_error_bits", "shk_insert_counted", "shk_dump", "shk_merge", "shk_multi_merge", "shk_import_shards", "shk_table_ptr", "shk_unitigs_add_reads",
            "shk_spectrum", "shk_inner_product", "shk_magnitude", "shk_intersect", "shk_count_fasta", "shk_split_batches", "shk_sample_chunks", "shk_query_fasta",
-           "shk_prefetch_passes", "shk_query_reads"]
+           "shk_prefetch_passes", "shk_query_reads", "shk_correct_reads", "shk_correct_lookups"]
 
 _libs = {}
 
@@ -154,6 +171,9 @@ def load(path=None):
     L.shk_count_fasta.argtypes = [vp, vp, i32, u64, i32, C.POINTER(BatchStats), C.POINTER(FastaStats)]
     L.shk_query_fasta.argtypes = [vp, vp, i32, u64, i32, u32, vp, u64, i32, vp, u32, C.POINTER(u32), C.POINTER(QueryStats)]
     L.shk_query_reads.argtypes = [vp, vp, i32, u64, pu64, pu64, u32, u32, u32, vp, u64, i32, pu64, vp, vp, u64, i32, pu64, C.POINTER(ReadsStats)]
+    L.shk_correct_reads.argtypes = [vp, vp, i32, u64, pu64, pu64, u32, u32, u32, u32, vp, u64, i32, pu64, vp, vp, i32, C.POINTER(CorrectStats)]
+    L.shk_correct_lookups.argtypes = [vp]
+    L.shk_correct_lookups.restype = u64
     L.shk_sample_chunks.argtypes = [vp, vp, i32, u64, pu64, pu64, u32, u32, C.POINTER(BatchStats), C.POINTER(SampleStats)]
     L.shk_hash_chunks.argtypes = [vp, vp, i32, u64, pu64, pu64, u32, C.POINTER(vp), pu64]
     L.shk_upload_text.argtypes = [vp, vp, u64, C.POINTER(vp)]
@@ -380,6 +400,42 @@ class Context:
         nr = nreads.value
         return (rs.as_dict(), rec[:nr].copy(), ext[:nr].copy() if want_extents else None,
                 track[:nwin.value].copy() if want_track else None)
+
+    def correct_reads(self, text, chunk_off, chunk_len, min_count=2, check=4, max_edits=8, want_extents=False,
+                      on_device=False, text_bytes=None):
+        """substitution errors of FASTQ chunks repaired against the table (shk_correct_reads); text as in count_chunks.
+        Returns (statistics dict, the reads' records as a structured array with CorrectRecord's fields, their extents as
+        one with ReadExtent's or None, the edits as an (nreads, max_edits) uint32 array of pos | code << 16 of which row
+        r's first records[r]["edits"] entries count). shk.correct.apply_edits puts them into the text. The call is
+        repeated once with larger arrays when it answers that there are more reads than the first guess."""
+        import numpy as np
+        if on_device or isinstance(text, int):
+            ptr, n = C.c_void_p(int(text)), int(text_bytes)
+        else:
+            buf = (C.c_char * max(len(text), 1)).from_buffer_copy(bytes(text) or b"\0") if not isinstance(text, C.Array) else text
+            ptr, n = C.cast(buf, C.c_void_p), len(text)
+        rec_cap = sum(int(x) for x in chunk_len) // 64 + 64
+        nreads, cs = C.c_uint64(), CorrectStats()
+        for _ in range(2):
+            rec = np.zeros(rec_cap, dtype=_struct_dtype(CorrectRecord))
+            ext = np.zeros(rec_cap, dtype=_struct_dtype(ReadExtent)) if want_extents else None
+            edits = np.zeros((rec_cap, int(max_edits)), dtype=np.uint32)
+            rc = self.L.shk_correct_reads(self.h, ptr, 1 if on_device else 0, n, self._tab(chunk_off), self._tab(chunk_len), len(chunk_off),
+                                          int(min_count), int(check), int(max_edits), C.c_void_p(rec.ctypes.data), rec_cap, 0,
+                                          C.byref(nreads), C.c_void_p(ext.ctypes.data) if want_extents else None,
+                                          C.c_void_p(edits.ctypes.data), 0, C.byref(cs))
+            if rc == -7 and nreads.value > rec_cap:
+                rec_cap = nreads.value
+                nreads.value = 0
+                continue
+            break
+        self._chk(rc)
+        nr = nreads.value
+        return cs.as_dict(), rec[:nr].copy(), ext[:nr].copy() if want_extents else None, edits[:nr].copy()
+
+    def correct_lookups(self):
+        """table lookups of the last correct_reads (measurement)"""
+        return int(self.L.shk_correct_lookups(self.h))
 
     def sample_chunks(self, text, chunk_off, chunk_len, sample_bits, on_device=False, text_bytes=None):
         """count the k-mers whose canonical hash has bits [hb, hb + sample_bits) zero (shk_sample_chunks); text as in
